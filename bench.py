@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """Headline benchmark: Criteo DeepFM training step, bs=65536 per GPU, on MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times exactly K steps and prints the headline line.  --full adds everything else this
+file measures: per-region kernel times and the roofline figures (from extra bracketed steps after the timed ones), the
+GEMM accuracy check, the CPU baselines and the other BASELINE configs (--no-cpu-baseline / --no-other-configs trim it).
+--dump-outputs DIR writes what the last timed step returned to its caller (loss, pred) as DIR/<name>.npy.
 
 Workload (BASELINE.json configs[1]): 26 sparse slots x 1M rows x dim 16 (one 26M-row table with
 slot offsets), 13 dense fields, top MLP 400-400-400 (config_bigdata.yaml:47), fp32, batch 65536.
@@ -258,6 +263,20 @@ def empty_bracket_us(dev, n=50):
     return sorted(ts)[len(ts) // 2]
 
 
+DUMP_MAX_ELEMS = 8 << 20        # per array: 32 MB of float32, so that loss + pred stay under 64 MB
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each array as out_dir/<name>.npy in float32.  An array of more than DUMP_MAX_ELEMS elements is
+    written as a fixed sample of them (the same seeded, sorted flat indices on every run); none at the default shapes."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.detach().to(torch.float32).cpu().numpy()
+        if a.size > DUMP_MAX_ELEMS:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(20250404).choice(a.size, DUMP_MAX_ELEMS, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def other_configs(timeout_s=120):
     """The other BASELINE configs measured in THIS run on THIS box (subprocesses of the repository's own tools, each under
     its own timeout; a failure is reported, never hidden, and never touches the main line): configs[2] DCN-v2 and
@@ -325,6 +344,8 @@ def other_configs(timeout_s=120):
                 job_env = dict(env, REC_DEEPFM_PIPELINED="1")
             if name.startswith("REC_GEMM_DIRECT=0"):      # every leading VAR=value of the name
                 job_env = dict(env, **dict(t.split("=", 1) for t in name.split(" bench.py")[0].split()))
+            if cmd[1] == os.path.abspath(__file__):       # this file: its kernels_ms / roofline are --full figures
+                cmd = cmd + ["--full"]
             r = subprocess.run(cmd + (["--no-other-configs"] if name.startswith("REC_GEMM_BF16X3=0") else []), cwd=REPO,
                                env=job_env, capture_output=True, text=True, timeout=timeout_s)
             lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -485,6 +506,18 @@ def self_spawn(n):
     return subprocess.call(cmd, env=env)
 
 
+def leave(dist, rank):
+    """Leave the process group together: a rank that tears its communicator down while a peer is still inside its last
+    collective takes that peer down with it (seen with 8 gloo ranks: "terminate called without an active exception")."""
+    if dist is None:
+        return
+    try:
+        dist.barrier()
+    except Exception as e:      # noqa: BLE001 - the line is out; a failed good-bye must not turn into a non-zero exit
+        print("[bench] rank %d: final barrier failed: %r" % (rank, e), file=sys.stderr)
+    dist.destroy_process_group()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -496,10 +529,15 @@ def main():
     ap.add_argument("--fc", type=str, default="400,400,400")
     ap.add_argument("--ids", choices=("uniform", "zipf"), default="uniform",
                     help="id distribution of SURVEY.md §8(d): (U) uniform [default] or (Z) Zipf 1.05 (hot rows)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: kernel / roofline breakdown, GEMM accuracy, CPU baselines and the other "
+                         "BASELINE configs (off: the plain run measures the timed steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the loss and predictions of the last timed step as DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true",
-                    help="skip the CPU baselines AND the other-configs section (quick runs, profiling)")
+                    help="--full: skip the CPU baselines AND the other-configs section (quick runs, profiling)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the BASELINE configs[2]/[3]/[4] + row-P measurements appended to the line at N = 1")
+                    help="--full: skip the BASELINE configs[2]/[3]/[4] + row-P measurements appended to the line at N = 1")
     ap.add_argument("--c-step", action="store_true",
                     help="issue every step through the one-call C entry point rec_deepfm_train_step (one stream; what a "
                          "non-Python binder gets) instead of the Python mirror's step")
@@ -660,33 +698,13 @@ def main():
     step_host = []
     for i in range(args.steps):
         h0 = time.perf_counter()
-        loss, _ = step(first + i)
+        loss, pred = step(first + i)
         step_host.append(time.perf_counter() - h0)
         host_issue += step_host[-1]
     barrier()
     dt = time.perf_counter() - t0
     if os.environ.get("REC_BENCH_STEP_TIMES"):       # diagnosis: host time of every step (ms) on stderr
         print("host ms per step: " + " ".join("%.2f" % (1e3 * x) for x in step_host), file=sys.stderr)
-    # per-region HIP-event timings (kernels_ms / host_issue_ms / in_step_event) come from a few MORE steps with the
-    # event brackets switched on — outside the timed region, which therefore carries no measurement markers
-    model.timers = None if standin else {}
-    n_brk = 0 if standin else min(args.steps, 10)
-    if dist is not None:
-        model.comm.stats = {}
-        if standin:
-            n_brk = 1
-    for i in range(n_brk):
-        step(first + args.steps + i)
-    sync()
-    exch = None
-    if dist is not None:
-        exch = model.comm.stats_summary(max(n_brk, 1))
-        model.comm.stats = None
-        for tag, e in exch.items():      # the link model next to the measurement (self-diagnosing first multi-GPU run)
-            e["measured_us"] = e.get("us_per_step")
-            e["predicted_us"] = round(link_model_us(tag, e["remote_bytes_per_step"], world, e["calls_per_step"]), 1)
-    if standin:
-        model.timers = {}
     if dist is not None:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -694,40 +712,8 @@ def main():
     ms = 1e3 * dt / args.steps
     loss_v = float(loss.item())
     oob = int(model.status.item())
-
-    def med(v):         # median over the bracketed steps: the first of them can carry a one-off host stall of tens of ms
-        v = sorted(v)   # (event pools / allocator growth when the brackets switch on) that lands in whichever region
-        return v[len(v) // 2] if v else 0.0   # it happens to hit and would dominate a mean over ten steps
-
-    def avg_ms(name):
-        return med([a.elapsed_time(b) for a, b in model.timers.get(name, [])])
-
-    k_ms = {k: avg_ms(k) for k in model.timers if not k.endswith("@host")}
-    host_ms = {k[:-5]: 1e3 * med(v) for k, v in model.timers.items() if k.endswith("@host")}
-    host_ms["step_issue_total"] = 1e3 * host_issue / args.steps     # host time inside train_step (no device sync)
-    # The roofline kernels once more, the way rocprofv3's kernel trace sees them: back-to-back launches between
-    # one pair of HIP events (no event markers / stream joins between the launches), on the step's own buffers.
-    pair_us = None
-    if dist is None and hasattr(model, "time_fm_pair") and not standin:
-        model.timers = None
-        pair_us = model.time_fm_pair([(b[0], b[1]) for b in batches], repeats=20, rounds=3)
-    fwd_b, bwd_b = algorithmic_bytes(B, S, Dn, D)
-    dfwd_b, dbwd_b = designed_bytes(B, S, Dn, D)
-    t_step_pair = (k_ms.get("fm_fwd", 0) + k_ms.get("fm_bwd", 0)) * 1e-3
-    in_step = (fwd_b + bwd_b) / t_step_pair / 1e9 if t_step_pair > 0 else 0.0
-    if pair_us is not None:
-        fwd_s, bwd_s = pair_us[0] * 1e-6, pair_us[1] * 1e-6
-        timing = "%d back-to-back launches per HIP-event pair, median of 3 (= the back-to-back population of rocprofv3's kernel trace; the in-step launches are roofline.in_step_event)" % 20
-    else:       # sharded path: only the in-step brackets exist
-        fwd_s, bwd_s = k_ms.get("fm_fwd", 0) * 1e-3, k_ms.get("fm_bwd", 0) * 1e-3
-        timing = "in-step HIP-event brackets"
-    achieved = (fwd_b + bwd_b) / (fwd_s + bwd_s) / 1e9 if fwd_s + bwd_s > 0 else 0.0
-    # flops EXECUTED: layer 0 runs on the folded [B,(S+1)D] input (DESIGN.md §3), not on the [B,(S+Dn)D] graph
-    model_compact = getattr(model, "compact", False)
-    sizes = [((S + 1) if model_compact else (S + Dn)) * D] + fc + [1]
-    t_gemm = (k_ms.get("mlp_fwd", 0) + k_ms.get("mlp_bwd", 0) + k_ms.get("mlp_bwd_dw0", 0)) * 1e-3
-    gemm_tf = 3 * mlp_flops(B, sizes) / t_gemm / 1e12 if k_ms.get("mlp_fwd") else 0.0
-    tr_f, tr_b, tr_src = pmc_traffic(B, D)
+    if args.dump_outputs and rank == 0:      # before any further step can overwrite what the last timed step returned
+        dump_outputs(args.dump_outputs, {"loss": loss, "pred": pred})
     out = {
         "metric": "CTR samples/sec, Criteo DeepFM bs=65536 (train step: fwd+bwd+optimizer)",
         "value": world * B * args.steps / dt, "unit": "samples/s", "n_gpus": world,
@@ -768,6 +754,67 @@ def main():
                                        "the --gpus 1 line (same table, same step, exchange degenerated to copies); the "
                                        "--gpus 1 headline value is configs[1] on the plain table"}
                       if dist is not None and args.table == "ps" else {})},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        leave(dist, rank)
+        return
+    # per-region HIP-event timings (kernels_ms / host_issue_ms / in_step_event) come from a few MORE steps with the
+    # event brackets switched on — outside the timed region, which therefore carries no measurement markers
+    model.timers = None if standin else {}
+    n_brk = 0 if standin else min(args.steps, 10)
+    if dist is not None:
+        model.comm.stats = {}
+        if standin:
+            n_brk = 1
+    for i in range(n_brk):
+        step(first + args.steps + i)
+    sync()
+    exch = None
+    if dist is not None:
+        exch = model.comm.stats_summary(max(n_brk, 1))
+        model.comm.stats = None
+        for tag, e in exch.items():      # the link model next to the measurement (self-diagnosing first multi-GPU run)
+            e["measured_us"] = e.get("us_per_step")
+            e["predicted_us"] = round(link_model_us(tag, e["remote_bytes_per_step"], world, e["calls_per_step"]), 1)
+    if standin:
+        model.timers = {}
+
+    def med(v):         # median over the bracketed steps: the first of them can carry a one-off host stall of tens of ms
+        v = sorted(v)   # (event pools / allocator growth when the brackets switch on) that lands in whichever region
+        return v[len(v) // 2] if v else 0.0   # it happens to hit and would dominate a mean over ten steps
+
+    def avg_ms(name):
+        return med([a.elapsed_time(b) for a, b in model.timers.get(name, [])])
+
+    k_ms = {k: avg_ms(k) for k in model.timers if not k.endswith("@host")}
+    host_ms = {k[:-5]: 1e3 * med(v) for k, v in model.timers.items() if k.endswith("@host")}
+    host_ms["step_issue_total"] = 1e3 * host_issue / args.steps     # host time inside train_step (no device sync)
+    # The roofline kernels once more, the way rocprofv3's kernel trace sees them: back-to-back launches between
+    # one pair of HIP events (no event markers / stream joins between the launches), on the step's own buffers.
+    pair_us = None
+    if dist is None and hasattr(model, "time_fm_pair") and not standin:
+        model.timers = None
+        pair_us = model.time_fm_pair([(b[0], b[1]) for b in batches], repeats=20, rounds=3)
+    fwd_b, bwd_b = algorithmic_bytes(B, S, Dn, D)
+    dfwd_b, dbwd_b = designed_bytes(B, S, Dn, D)
+    t_step_pair = (k_ms.get("fm_fwd", 0) + k_ms.get("fm_bwd", 0)) * 1e-3
+    in_step = (fwd_b + bwd_b) / t_step_pair / 1e9 if t_step_pair > 0 else 0.0
+    if pair_us is not None:
+        fwd_s, bwd_s = pair_us[0] * 1e-6, pair_us[1] * 1e-6
+        timing = "%d back-to-back launches per HIP-event pair, median of 3 (= the back-to-back population of rocprofv3's kernel trace; the in-step launches are roofline.in_step_event)" % 20
+    else:       # sharded path: only the in-step brackets exist
+        fwd_s, bwd_s = k_ms.get("fm_fwd", 0) * 1e-3, k_ms.get("fm_bwd", 0) * 1e-3
+        timing = "in-step HIP-event brackets"
+    achieved = (fwd_b + bwd_b) / (fwd_s + bwd_s) / 1e9 if fwd_s + bwd_s > 0 else 0.0
+    # flops EXECUTED: layer 0 runs on the folded [B,(S+1)D] input (DESIGN.md §3), not on the [B,(S+Dn)D] graph
+    model_compact = getattr(model, "compact", False)
+    sizes = [((S + 1) if model_compact else (S + Dn)) * D] + fc + [1]
+    t_gemm = (k_ms.get("mlp_fwd", 0) + k_ms.get("mlp_bwd", 0) + k_ms.get("mlp_bwd_dw0", 0)) * 1e-3
+    gemm_tf = 3 * mlp_flops(B, sizes) / t_gemm / 1e12 if k_ms.get("mlp_fwd") else 0.0
+    tr_f, tr_b, tr_src = pmc_traffic(B, D)
+    out.update({
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBS,
                      "traffic": (tr_f + tr_b) if tr_f is not None else None,
@@ -817,7 +864,7 @@ def main():
                      if X3_ON else "exact f32 MFMA",
                      "f32_mfma_peak": FP32_MFMA_PEAK_TF, "vs_f32_mfma_peak": gemm_tf / FP32_MFMA_PEAK_TF,
                      "flops_executed_per_step": 3 * mlp_flops(B, sizes)},
-    }
+    })
     if rank == 0 and not standin and dev.type == "cuda":
         try:
             out["mlp_gemm"]["error_vs_float64"] = gemm_accuracy(dev)
@@ -842,14 +889,7 @@ def main():
                 torch.cuda.empty_cache()
                 out["other_configs"] = other_configs()
         print(json.dumps(out), flush=True)
-    if dist is not None:
-        # leave together: a rank that tears its communicator down while a peer is still inside its last collective
-        # takes that peer down with it (seen with 8 gloo ranks: "terminate called without an active exception")
-        try:
-            dist.barrier()
-        except Exception as e:      # noqa: BLE001 - the line is out; a failed good-bye must not turn into a non-zero exit
-            print("[bench] rank %d: final barrier failed: %r" % (rank, e), file=sys.stderr)
-        dist.destroy_process_group()
+    leave(dist, rank)
 
 
 if __name__ == "__main__":

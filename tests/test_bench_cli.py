@@ -51,11 +51,42 @@ def test_plain_command_line_adam_table_two_ranks():
 
 
 def test_single_rank_line_and_contract_keys():
-    d = _run(["--rows-per-table", "300"] + SMALL)
+    d = _run(["--rows-per-table", "300", "--full"] + SMALL)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline"):
         assert k in d, k
     assert d["n_gpus"] == 1 and d["vs_baseline"] is None and d["dtype"].startswith("f32")
+
+
+def test_plain_line_is_the_headline_only():
+    """Without --full the line carries the headline and the run's config, none of the extra measurements."""
+    d = _run(["--rows-per-table", "300"] + SMALL)
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config"):
+        assert k in d, k
+    for k in ("roofline", "kernels_ms", "host_issue_ms", "mlp_gemm", "cpu_baseline", "other_configs"):
+        assert k not in d, k
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    assert abs(d["value"] - 64 * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+
+
+def test_dump_outputs_writes_the_last_timed_step_reproducibly(tmp_path):
+    """--dump-outputs DIR: the loss and predictions of the last timed step as float32 .npy files; the same arguments
+    give the same inputs, so two runs of one build write the same arrays."""
+    import numpy as np
+    runs = []
+    for k in range(2):
+        out = tmp_path / ("run%d" % k)
+        d = _run(["--rows-per-table", "300", "--dump-outputs", str(out)] + SMALL)
+        assert sorted(os.listdir(out)) == ["loss.npy", "pred.npy"]
+        loss, pred = np.load(out / "loss.npy"), np.load(out / "pred.npy")
+        assert loss.dtype == np.float32 and pred.dtype == np.float32
+        assert loss.size == 1 and pred.shape == (64, 1)
+        assert np.isfinite(pred).all() and ((pred > 0) & (pred < 1)).all()
+        assert abs(float(loss.reshape(-1)[0]) - d["config"]["loss"]) <= 1e-6 * abs(d["config"]["loss"])
+        runs.append((loss, pred))
+    np.testing.assert_array_equal(runs[0][0], runs[1][0])
+    np.testing.assert_array_equal(runs[0][1], runs[1][1])
 
 
 def test_world_size_mismatch_is_refused():
@@ -69,7 +100,7 @@ def test_eight_ranks_on_the_ps_table_print_the_exchange_fields():
     """nothing had run with more than 2 ranks.  `python bench.py --gpus 8` as the driver starts it
     (gloo stand-in): eight ranks rendezvous, shard the hashed table 8 ways, and rank 0's line carries the per-collective
     exchange fields — the three all-to-alls (ids, rows, gradients) and the dense all-reduce with bytes per step."""
-    d = _run(["--gpus", "8"] + SMALL + ["--hashed-rows", "2000"], timeout=900)
+    d = _run(["--gpus", "8", "--full"] + SMALL + ["--hashed-rows", "2000"], timeout=900)
     assert d["n_gpus"] == 8 and d["config"]["global_batch"] == 8 * 64 and d["config"]["table_rows_total"] == 16000
     assert "rowshard8+dp8" in d["config"]["parallelism"] and d["config"]["index_oob_flag"] == 0
     ex = d["exchange"]

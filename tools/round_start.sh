@@ -7,11 +7,11 @@ out=$root/gpurun_out/round_start
 mkdir -p $out
 cd $root
 echo "== gpu tests";      timeout 300 python -m pytest tests -m gpu -q -x > $out/pytest_gpu.log 2>&1; tail -3 $out/pytest_gpu.log
-echo "== bench";          timeout 200 python -u bench.py 2>/dev/null | grep "^{" > $out/bench.json; cut -c1-200 $out/bench.json
+echo "== bench";          timeout 200 python -u bench.py --full 2>/dev/null | grep "^{" > $out/bench.json; cut -c1-200 $out/bench.json
 echo "== sharded path, world 1 (12 and 30 steps, tail modes)"
 for steps in 12 30; do
   for mode in overlap serial; do
-    REC_SHARD_TAIL=$mode timeout 120 python -u bench.py --steps $steps --warmup 3 --force-sharded --no-cpu-baseline 2>/dev/null \
+    REC_SHARD_TAIL=$mode timeout 120 python -u bench.py --full --steps $steps --warmup 3 --force-sharded --no-cpu-baseline 2>/dev/null \
       | grep "^{" > $out/sharded_${mode}_$steps.json
     python - "$out/sharded_${mode}_$steps.json" "$mode" "$steps" <<'PY'
 import json, sys

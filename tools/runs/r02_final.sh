@@ -13,11 +13,11 @@ timeout 400 rocprofv3 --kernel-trace --stats -d $out/models -o m --output-format
 timeout 300 rocprofv3 --kernel-trace --stats -d $out/slot -o s --output-format csv -- python $root/tools/slot_dnn_bench.py > $out/slot_dnn.txt 2>&1; echo "slot trace rc=$?"
 cd $root
 find $out -name "*kernel_trace.csv" -delete
-timeout 300 python -u bench.py 2>/dev/null | grep "^{" > $out/bench.json
-timeout 300 python -u bench.py --force-sharded --no-cpu-baseline 2>/dev/null | grep "^{" > $out/bench_force_sharded.json
-timeout 600 python -u bench.py --table ps --no-cpu-baseline 2>/dev/null | grep "^{" > $out/bench_ps.json
-timeout 300 python -u bench.py --shared-table --dim 9 --no-cpu-baseline 2>/dev/null | grep "^{" > $out/bench_shared_D9.json
-timeout 300 python -u bench.py --ids zipf --no-cpu-baseline 2>/dev/null | grep "^{" > $out/bench_zipf.json
+timeout 300 python -u bench.py --full 2>/dev/null | grep "^{" > $out/bench.json
+timeout 300 python -u bench.py --full --force-sharded --no-cpu-baseline 2>/dev/null | grep "^{" > $out/bench_force_sharded.json
+timeout 600 python -u bench.py --full --table ps --no-cpu-baseline 2>/dev/null | grep "^{" > $out/bench_ps.json
+timeout 300 python -u bench.py --full --shared-table --dim 9 --no-cpu-baseline 2>/dev/null | grep "^{" > $out/bench_shared_D9.json
+timeout 300 python -u bench.py --full --ids zipf --no-cpu-baseline 2>/dev/null | grep "^{" > $out/bench_zipf.json
 python - <<'PY'
 import json, glob
 for f in sorted(glob.glob("gpurun_out/r02_final/bench*.json")):

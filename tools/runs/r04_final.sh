@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/r04final; mkdir -p "$O"; cd "$R"
 timeout 900 python -m pytest tests -m gpu -x -q 2>&1 | tail -6 > "$O/pytest_gpu.txt"
 timeout 200 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2 >> "$O/pytest_gpu.txt"
 cat "$O/pytest_gpu.txt"
-timeout 900 python bench.py 2> "$O/bench.err" | tail -1 > "$O/bench_line.json"
+timeout 900 python bench.py --full 2> "$O/bench.err" | tail -1 > "$O/bench_line.json"
 cut -c1-400 "$O/bench_line.json"
 bash tools/profile_bench.sh r04 > "$O/profile.log" 2>&1
 tail -5 "$O/profile.log"

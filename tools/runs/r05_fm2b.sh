@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/r05_fm2b; mkdir -p "$O"; cd "$R"
 for D in 9 10; do
 for cfg in "0 32" "1 32" "0 16" "1 16"; do
   set -- $cfg
-  REC_FM_TILE=$1 REC_TABLE_RECORD_FLOATS=$2 timeout 300 python bench.py --shared-table --dim $D --no-cpu-baseline --no-other-configs --steps 20 --warmup 5 > $O/d${D}_tile$1_rec$2.json 2> $O/d${D}_tile$1_rec$2.err
+  REC_FM_TILE=$1 REC_TABLE_RECORD_FLOATS=$2 timeout 300 python bench.py --full --shared-table --dim $D --no-cpu-baseline --no-other-configs --steps 20 --warmup 5 > $O/d${D}_tile$1_rec$2.json 2> $O/d${D}_tile$1_rec$2.err
   python - "$O/d${D}_tile$1_rec$2.json" $D $1 $2 <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); r = d["roofline"]; pk = r["per_kernel"]

@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/x3; mkdir -p "$O"; cd "$R"
 timeout 900 python -m pytest tests -m gpu -q 2>&1 | tail -8 | tee "$O/suite_default_on.txt"
 timeout 200 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2 | tee -a "$O/suite_default_on.txt"
-timeout 900 python bench.py 2> "$O/bench.err" | tail -1 > "$O/bench_line.json"
+timeout 900 python bench.py --full 2> "$O/bench.err" | tail -1 > "$O/bench_line.json"
 python - <<'P'
 import json
 d=json.load(open("gpurun_out/x3/bench_line.json"))

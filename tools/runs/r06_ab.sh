@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/r06ab; mkdir -p "$O"; cd "$R"
 for i in 1 2 3; do for spec in "$@"; do
   tag=${spec%%:*}; envs=$(echo "${spec#*:}" | tr ',' ' ')
-  env $envs timeout 300 python bench.py --no-other-configs --no-cpu-baseline 2>"$O/$tag.err" | tail -1 > "$O/$tag.json"
+  env $envs timeout 300 python bench.py --full --no-other-configs --no-cpu-baseline 2>"$O/$tag.err" | tail -1 > "$O/$tag.json"
   python - "$O/$tag.json" "$tag" <<'PY'
 import json,sys
 try:

@@ -6,7 +6,7 @@ timeout 1200 python -m pytest tests/test_gemm_gpu.py tests/test_deepfm_gpu.py te
 for i in 1 2 3; do
   for v in 0 1; do
     echo -n "REC_RELU_BITS=$v  "
-    REC_RELU_BITS=$v timeout 600 python bench.py --no-other-configs --no-cpu-baseline 2>> "$O/bench.err" | tail -1 | \
+    REC_RELU_BITS=$v timeout 600 python bench.py --full --no-other-configs --no-cpu-baseline 2>> "$O/bench.err" | tail -1 | \
       python -c "import json,sys; d=json.loads(sys.stdin.read()); print('ms_per_step %.4f' % d['ms_per_step'], {k: round(v, 4) for k, v in d['kernels_ms'].items()}, 'loss', d['config'].get('loss'))"
   done
 done | tee "$O/ab.txt"
