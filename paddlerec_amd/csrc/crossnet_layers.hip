@@ -37,7 +37,7 @@ struct Carve {   // bump allocator over the caller's workspace (256-B aligned pi
 };
 
 static rec_gemm_desc gd(int64_t m, int n, int k, int lda, int ldb, int ldc, int ta, int tb, int epi) {
-  rec_gemm_desc d;
+  rec_gemm_desc d{};                     // num_cus 0 (x3_dw_eligible plans on every CU), split_k 0
   d.m = m; d.n = n; d.k = k; d.lda = lda; d.ldb = ldb; d.ldc = ldc;
   d.trans_a = ta; d.trans_b = tb; d.epilogue = epi; d.split_k = 0;
   return d;

@@ -787,6 +787,236 @@ __global__ __launch_bounds__(256) void gemm_bf16x3_dw_kernel(X3DwArgs w) {
   }
 }
 
+// Weight-gradient form 1 (REC_X3_DW_FORM, the default): the same block, slices, LDS image and arithmetic as
+// gemm_bf16x3_dw_kernel, on EIGHT waves — two per SIMD, 256 registers each — so that one wave's conversion, LDS stores,
+// fragment waits and barrier sit beside its SIMD partner's MFMAs instead of idling the matrix pipe.  The 13 x 13-tile
+// output block goes 4 (Kin) x 2 (Nout) over the waves: a wave holds its <= 4 X tiles' fragments (48 registers), streams
+// the 7 G tiles double-buffered (24) and accumulates <= 4 x 7 tiles (112).  Kin quarters are split as evenly as they come
+// (13 = 4 + 3 + 3 + 3) and the wave runs a body compiled for its own count (PW or PW - 1 X tiles); waves w and w + 4 take
+// quarters w and 3 - w, so that a SIMD's two waves (round-robin placement) hold 7 or 6 X tiles between them, never 8.
+// Staging: thread t of waves 0..3 owns the X patch (m-group s / 52, column group s % 52), s = t, of waves 4..7 the G patch,
+// s = t - 256 — 8 rows x 4 columns, 32 registers — and writes each column's three planes (the old form: both operands'
+// six).  Every product runs in the old form's order on the same operands: P and the column sums are bit-identical to it.
+template <int PW>
+struct X3Dw8Acc { f32x4_t v[PW][kX3DwWT]; };
+
+// per-thread state of gemm_bf16x3_dw_kernel_w8: its patch, LDS addresses and partial-tile destination
+struct X3Dw8Ctx {
+  const float* src; int64_t ld; bool ok;
+  char* base; unsigned wr_off[4];
+  unsigned xb[4], gb[4];
+  float4 raw[8];
+  float4 csum;
+  float* P; int64_t ldp; int kin, nout, k_tile0, n_tile0, my_k0, my_n0, my_p, my_q, li, g;
+  __device__ __forceinline__ void load_patch(int kt) {
+#pragma unroll
+    for (int r = 0; r < 8; ++r) raw[r] = *reinterpret_cast<const float4*>(src + ((int64_t)kt * 32 + r) * ld);
+  }
+  // column e of the patch -> its three 16-B plane chunks (and, for G, the column's running sum: X's is never read)
+  __device__ __forceinline__ void convert(int e, u32x4_t (&ch)[3]) {
+    float v[8];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) v[r] = e == 0 ? raw[r].x : e == 1 ? raw[r].y : e == 2 ? raw[r].z : raw[r].w;
+    asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]));
+    float cs = 0.f;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+      const float u0 = ok ? v[2 * d] : 0.f, u1 = ok ? v[2 * d + 1] : 0.f;
+      cs += u0 + u1;
+      unsigned a, b, cc;
+      x3_split_pair(u0, u1, a, b, cc);
+      ch[0][d] = a; ch[1][d] = b; ch[2][d] = cc;
+    }
+    if (e == 0) csum.x += cs; else if (e == 1) csum.y += cs; else if (e == 2) csum.z += cs; else csum.w += cs;
+  }
+  __device__ __forceinline__ void write(int stage, int e, const u32x4_t (&ch)[3]) {
+    char* p = base + stage * kX3Stage + wr_off[e];
+    *reinterpret_cast<u32x4_t*>(p) = ch[0];
+    *reinterpret_cast<u32x4_t*>(p + kX3DwPlane) = ch[1];
+    *reinterpret_cast<u32x4_t*>(p + 2 * kX3DwPlane) = ch[2];
+  }
+  // lane (i, g) holds P[Kin = tile a, row i][Nout = tile t, columns 4g .. 4g+3]
+  template <int NP>
+  __device__ __forceinline__ void store(const f32x4_t (&acc)[NP][kX3DwWT]) {
+#pragma unroll
+    for (int a = 0; a < NP; ++a) {
+      if (a >= my_p) continue;
+      const int ki = (k_tile0 + my_k0 + a) * 16 + li;
+#pragma unroll
+      for (int t = 0; t < kX3DwWT; ++t) {
+        if (t >= my_q) continue;
+        const int nj = (n_tile0 + my_n0 + t) * 16 + g * 4;
+        if (ki < kin && nj < nout) *reinterpret_cast<f32x4_t*>(P + (int64_t)ki * ldp + nj) = acc[a][t];
+      }
+    }
+  }
+};
+
+template <int PW>
+__device__ __forceinline__ void x3_dw8_run(X3Dw8Ctx& c, int nsteps) {
+  X3Dw8Acc<PW> acc;
+#pragma unroll
+  for (int a = 0; a < PW; ++a)
+#pragma unroll
+    for (int t = 0; t < kX3DwWT; ++t) acc.v[a][t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  // One k-step.  MORE: there is a next step — its patch is loaded at the top, and its four columns are converted under
+  // tiles 2..5 and stored (three ds_write_b128 each) under tiles 3..6 of this step's MFMA stream.
+  auto step = [&](int kt, auto more_c) {
+    constexpr bool MORE = decltype(more_c)::value;
+    const int stage = kt & 1;
+    if (MORE) c.load_patch(kt + 1);
+    __builtin_amdgcn_sched_barrier(0);
+    const unsigned so = stage * kX3Stage;
+    u32x4_t af[PW][3];
+    u32x4_t bf[2][3];
+    u32x4_t pend[3];
+    x3_dw_read_u(bf[0], c.gb[0] + so, 0);
+#pragma unroll
+    for (int u = 0; u < PW; ++u) x3_dw_read_u(af[u], c.xb[u & 3] + so, u);
+    x3_dw_read_u(bf[1], c.gb[1] + so, 1);
+#pragma unroll
+    for (int a = 0; a < PW; ++a) {                          // tile 0 row tile by row tile behind counted waits
+      x3_dw_wait_frags(af[a], 3 * (PW - 1 - a) + 3);
+      const u32x4_t* b0 = bf[0];
+#define REC_X3_DW8_MFMA0(PB, PA)                                                                               \
+  acc.v[a][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, b0[PB]),                  \
+                                                        __builtin_bit_cast(bf16x8_t, af[a][PA]), acc.v[a][0], 0, 0, 0);
+#if REC_X3_PRODUCTS >= 6
+      REC_X3_DW8_MFMA0(2, 0) REC_X3_DW8_MFMA0(1, 1) REC_X3_DW8_MFMA0(0, 2)
+#endif
+#if REC_X3_PRODUCTS >= 3
+      REC_X3_DW8_MFMA0(1, 0) REC_X3_DW8_MFMA0(0, 1)
+#endif
+      REC_X3_DW8_MFMA0(0, 0)
+#undef REC_X3_DW8_MFMA0
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int t = 1; t < kX3DwWT; ++t) {
+      if (t + 1 < kX3DwWT) {
+        x3_dw_read_u(bf[(t + 1) & 1], c.gb[(t + 1) & 3] + so, t + 1);
+        asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(bf[t & 1][0]), "+v"(bf[t & 1][1]), "+v"(bf[t & 1][2]));
+      } else {
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(bf[t & 1][0]), "+v"(bf[t & 1][1]), "+v"(bf[t & 1][2]));
+      }
+      const u32x4_t* b = bf[t & 1];
+#define REC_X3_DW8_MFMA(PB, PA)                                                                                \
+  _Pragma("unroll") for (int a = 0; a < PW; ++a) acc.v[a][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(        \
+      __builtin_bit_cast(bf16x8_t, b[PB]), __builtin_bit_cast(bf16x8_t, af[a][PA]), acc.v[a][t], 0, 0, 0);
+#if REC_X3_PRODUCTS >= 6
+      REC_X3_DW8_MFMA(2, 0) REC_X3_DW8_MFMA(1, 1) REC_X3_DW8_MFMA(0, 2)
+#endif
+#if REC_X3_PRODUCTS >= 3
+      REC_X3_DW8_MFMA(1, 0) REC_X3_DW8_MFMA(0, 1)
+#endif
+      REC_X3_DW8_MFMA(0, 0)
+#undef REC_X3_DW8_MFMA
+      if (MORE && t >= kX3DwWT - 5) {
+        const bool wr = t >= kX3DwWT - 4, cv = t <= kX3DwWT - 2;
+        if (wr) c.write(stage ^ 1, t - (kX3DwWT - 4), pend);
+        if (cv) c.convert(t - (kX3DwWT - 5), pend);
+#pragma unroll
+        for (int i = 0; i < 6 * PW; ++i) {
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // one MFMA
+          if (cv) __builtin_amdgcn_sched_group_barrier(0x002, REC_X3_DW_VALU_PER_MFMA, 0);
+          if (wr && i % (2 * PW) == PW) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);   // one ds_write_b128
+        }
+        if (cv) __builtin_amdgcn_sched_group_barrier(0x002, 32, 0);       // what is left of the conversion
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    __syncthreads();
+  };
+  for (int kt = 0; kt + 1 < nsteps; ++kt) step(kt, std::true_type{});
+  if (nsteps > 0) step(nsteps - 1, std::false_type{});
+  c.store(acc.v);
+}
+
+template <int PW>      // X tiles of the larger Kin quarter (ceil(kb_tiles / 4): 4 or 3); a wave runs PW or PW - 1
+__global__ __launch_bounds__(512) void gemm_bf16x3_dw_kernel_w8(X3DwArgs w) {
+  static_assert(PW >= 2 && PW <= 4, "four X tiles at most fit the 256-register budget");
+  extern __shared__ __attribute__((aligned(1024))) char x3_smem[];
+  const int tid = threadIdx.x;
+  const int lane = tid % kWave;
+  const int wave = __builtin_amdgcn_readfirstlane(tid / kWave);
+  const int li = lane & 15, g = lane >> 4;
+  const int wk = wave < 4 ? wave : 7 - wave, wn = wave >> 2;
+  const int nob = w.kblocks * w.nblocks;
+  const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
+  const int ob = j % nob, slice = (j / nob) * 8 + xcd;
+  const int kb = ob / w.nblocks, nb = ob % w.nblocks;
+  const int k_tile0 = kb * w.kb_tiles, n_tile0 = nb * w.nb_tiles;
+  const int kt_blk = min(w.kb_tiles, (w.kin + 15) / 16 - k_tile0);
+  const int nt_blk = min(w.nb_tiles, (w.nout + 15) / 16 - n_tile0);
+  const int n_split = (nt_blk + 1) / 2;                                                   // as in the old form
+  const int kq = kt_blk >> 2, kr = kt_blk & 3;                                            // Kin quarters: kq + (wk < kr)
+  const int my_k0 = wk * kq + min(wk, kr), my_p = __builtin_amdgcn_readfirstlane(kq + (wk < kr ? 1 : 0));
+  const int my_n0 = wn ? n_split : 0, my_q = __builtin_amdgcn_readfirstlane(wn ? nt_blk - n_split : n_split);
+  const int64_t row0 = (int64_t)slice * w.steps_per_slice * 32;
+  int nsteps = (int)min((int64_t)w.steps_per_slice, (w.rows - row0) / 32);
+  if (nsteps < 0) nsteps = 0;
+
+  // ---- staging: operand op (0 X, 1 G) from the wave's half of the block, s < 208 owns patch (s / 52, s % 52)
+  // The 48 threads of a half without a patch of their own (s >= 208) repeat patch s - 208: the same loads, the same
+  // chunks stored to the same LDS slots (identical data), so that staging is straight-line code with constant offsets.
+  const int op = wave >> 2, s = tid & 255;
+  const bool stager = s < 4 * (kX3DwCols / 4);
+  const int sp = stager ? s : s - 4 * (kX3DwCols / 4);
+  const int mg = sp / (kX3DwCols / 4), cg = sp % (kX3DwCols / 4);
+  const int col = (op ? n_tile0 : k_tile0) * 16 + cg * 4;
+  const bool ok = cg * 4 < (op ? nt_blk : kt_blk) * 16 && col < (op ? w.nout : w.kin);
+  const int64_t ld = op ? w.ldg : w.ldx;
+  const float* src = (op ? w.G : w.X) + (row0 + mg * 8) * ld + (ok ? col : 0);
+
+  X3Dw8Ctx c;
+  c.src = src; c.ld = ld; c.ok = ok;
+  c.base = x3_smem + op * kX3DwOperand;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int a = cg >> 2, i = 4 * (cg & 3) + e;
+    c.wr_off[e] = (unsigned)((mg * kX3DwCols + 16 * a + x3_dw_q(i, a)) * 16);
+  }
+  c.csum = make_float4(0.f, 0.f, 0.f, 0.f);
+  const unsigned lds0 = (unsigned)(uintptr_t)x3_smem;
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int ax = my_k0 + u, an = my_n0 + u;
+    c.xb[u] = lds0 + (unsigned)((g * kX3DwCols + 16 * my_k0 + x3_dw_q(li, ax)) * 16);
+    c.gb[u] = lds0 + kX3DwOperand + (unsigned)((g * kX3DwCols + 16 * my_n0 + x3_dw_q(li, an)) * 16);
+  }
+  c.P = w.P + (int64_t)slice * w.kin * w.ldp; c.ldp = w.ldp; c.kin = w.kin; c.nout = w.nout; c.k_tile0 = k_tile0; c.n_tile0 = n_tile0; c.my_k0 = my_k0; c.my_n0 = my_n0;
+  c.my_p = my_p; c.my_q = my_q; c.li = li; c.g = g;
+
+  if (nsteps > 0) {
+    c.load_patch(0);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      u32x4_t ch[3];
+      c.convert(e, ch);
+      c.write(0, e, ch);
+    }
+  }
+  __syncthreads();
+  if (my_p == PW) x3_dw8_run<PW>(c, nsteps);          // wave-uniform: both bodies meet the same barriers
+  else x3_dw8_run<PW - 1>(c, nsteps);
+
+  // ---- column sums of G's slice: the four m-groups of a column group meet in LDS (every stage is free now)
+  if (w.cpart && kb == 0) {
+    float4* red = reinterpret_cast<float4*>(x3_smem);
+    if (op == 1 && stager) red[mg * (kX3DwCols / 4) + cg] = c.csum;
+    __syncthreads();
+    if (tid < kX3DwCols / 4 && tid * 4 < nt_blk * 16 && n_tile0 * 16 + tid * 4 < w.nout) {
+      const float4 s0 = red[tid], s1 = red[kX3DwCols / 4 + tid], s2 = red[2 * (kX3DwCols / 4) + tid],
+                   s3 = red[3 * (kX3DwCols / 4) + tid];
+      float4 o;
+      o.x = (s0.x + s1.x) + (s2.x + s3.x); o.y = (s0.y + s1.y) + (s2.y + s3.y);
+      o.z = (s0.z + s1.z) + (s2.z + s3.z); o.w = (s0.w + s1.w) + (s2.w + s3.w);
+      *reinterpret_cast<float4*>(w.cpart + (int64_t)slice * w.nout + n_tile0 * 16 + tid * 4) = o;
+    }
+  }
+}
+
 // host side -------------------------------------------------------------------------------------------------------
 inline int x3_launch_split(const float* W, int64_t ldw, int K, int N, int trans, char* img, hipStream_t st) {
   const X3Cols c = x3_cols(N);
@@ -907,19 +1137,23 @@ inline bool x3_dw_plan(int kin, int nout, int64_t rows, int cus, X3DwPlan* p) {
   p->slices = (p->slices + 7) / 8 * 8;             // whole groups of 8 (slices behind the rows write zeros)
   return true;
 }
+#ifndef REC_X3_DW_FORM_DEFAULT
+#define REC_X3_DW_FORM_DEFAULT 1      // 1: gemm_bf16x3_dw_kernel_w8 (eight waves), 0: gemm_bf16x3_dw_kernel (four waves)
+#endif
+template <typename K>
+inline bool x3_dw_lds_attr(K kernel, int lds) {
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess;
+}
+// form: 0 the four-wave kernel, 1 the eight-wave kernel, < 0 REC_X3_DW_FORM (read once; default REC_X3_DW_FORM_DEFAULT).
+// Both take the same plan, workspace and LDS, and give bit-identical results.
 inline int x3_launch_dw(const X3DwPlan& pl, int kin, int nout, int64_t rows, const float* X, int64_t ldx, const float* G,
-                        int64_t ldg, float* P, int64_t ldp, float* cpart, hipStream_t st) {
+                        int64_t ldg, float* P, int64_t ldp, float* cpart, hipStream_t st, int form = -1) {
   static std::atomic<bool> attr_set{false};
   constexpr int lds = 2 * kX3Stage + 4096;        // + a 16-B slot per thread for the patch-less threads' stores
   if (!attr_set.load(std::memory_order_acquire)) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16x3_dw_kernel<7, true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16x3_dw_kernel<5, true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16x3_dw_kernel<7, false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16x3_dw_kernel<5, false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
+    if (!x3_dw_lds_attr(&gemm_bf16x3_dw_kernel<7, true>, lds) || !x3_dw_lds_attr(&gemm_bf16x3_dw_kernel<5, true>, lds) ||
+        !x3_dw_lds_attr(&gemm_bf16x3_dw_kernel<7, false>, lds) || !x3_dw_lds_attr(&gemm_bf16x3_dw_kernel<5, false>, lds) ||
+        !x3_dw_lds_attr(&gemm_bf16x3_dw_kernel_w8<4>, lds) || !x3_dw_lds_attr(&gemm_bf16x3_dw_kernel_w8<3>, lds)) {
       (void)hipGetLastError();
       set_error("gemm_bf16x3_dw: %d B of dynamic LDS refused", lds);
       return REC_EHIP;
@@ -929,6 +1163,17 @@ inline int x3_launch_dw(const X3DwPlan& pl, int kin, int nout, int64_t rows, con
   X3DwArgs w{X, ldx, G, ldg, rows, kin, nout, pl.kb_tiles, pl.nb_tiles, pl.kblocks, pl.nblocks, pl.slices,
              pl.steps_per_slice, P, ldp, cpart};
   const unsigned grid = (unsigned)(pl.slices * pl.kblocks * pl.nblocks);
+  static const int env_form = [] {
+    const char* v = getenv("REC_X3_DW_FORM");
+    return v && *v ? (*v != '0' ? 1 : 0) : REC_X3_DW_FORM_DEFAULT;
+  }();
+  if ((form < 0 ? env_form : form) != 0) {
+    // the larger Kin quarter: 13 / 12 -> 4 / 3 tiles; smaller blocks take the 3-tile kernel (waves with fewer tiles
+    // multiply whatever their spare LDS slots hold and store nothing of it)
+    if ((pl.kb_tiles + 3) / 4 >= 4) hipLaunchKernelGGL((gemm_bf16x3_dw_kernel_w8<4>), dim3(grid), dim3(512), lds, st, w);
+    else hipLaunchKernelGGL((gemm_bf16x3_dw_kernel_w8<3>), dim3(grid), dim3(512), lds, st, w);
+    return check_launch("gemm_bf16x3_dw_kernel_w8");
+  }
   // REC_X3_DW_PIPE=0: the round-5 schedule (a column's six LDS stores in one burst behind its conversion) for A/B runs
   static const bool pipe = [] { const char* v = getenv("REC_X3_DW_PIPE"); return v && *v ? *v != '0' : REC_X3_DW_PIPE_STORES != 0; }();
   const bool p5 = (pl.kb_tiles + 1) / 2 <= 5;

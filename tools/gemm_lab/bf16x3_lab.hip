@@ -29,3 +29,11 @@ extern "C" int lab_x3_dw(int kin, int nout, int64_t rows, const float* X, int64_
   if (slices_out) *slices_out = pl.slices;
   return x3_launch_dw(pl, kin, nout, rows, X, ldx, G, ldg, P, ldp, cpart, (hipStream_t)stream);
 }
+// the same with the kernel form named (0: four waves, 1: eight waves) — interleaved A/B runs in one process
+extern "C" int lab_x3_dw_form(int form, int kin, int nout, int64_t rows, const float* X, int64_t ldx, const float* G,
+                              int64_t ldg, float* P, int64_t ldp, float* cpart, int* slices_out, void* stream) {
+  X3DwPlan pl;
+  if (!x3_dw_plan(kin, nout, rows, 256, &pl)) return -1;
+  if (slices_out) *slices_out = pl.slices;
+  return x3_launch_dw(pl, kin, nout, rows, X, ldx, G, ldg, P, ldp, cpart, (hipStream_t)stream, form);
+}

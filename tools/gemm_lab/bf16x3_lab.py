@@ -2,7 +2,8 @@
 """csrc/gemm_bf16x3.h (f32 GEMM as six bf16 MFMAs per product, exact three-way operand split) built alone, against the
 engine's exact-f32 tiled kernels and a float64 product.
 
-    bash tools/gemm_lab/build_x3.sh && python tools/gemm_lab/bf16x3_lab.py [--iters 20] [--rounds 3] [--data rand|ones|zeros]"""
+    bash tools/gemm_lab/build_x3.sh && python tools/gemm_lab/bf16x3_lab.py [--iters 20] [--rounds 3] [--data rand|ones|zeros]
+    python tools/gemm_lab/bf16x3_lab.py --dwab [--rounds 5]     (weight-gradient kernel alone: form 0 against form 1)"""
 import argparse
 import ctypes as C
 import os
@@ -163,7 +164,51 @@ def dwk_main(args):
               flush=True)
 
 
+def dwab_main(args):
+    """the weight-gradient kernel alone, form 0 (four waves) against form 1 (eight waves), interleaved: best of the
+    rounds, the float64 bound of each, and whether the partial tiles are bit-identical"""
+    lab = C.CDLL(args.lib)
+    g = torch.Generator(device="cuda").manual_seed(2)
+    rnd = lambda *s: torch.rand(*s, device="cuda", generator=g) - 0.5
+    st = torch.cuda.current_stream().cuda_stream
+    p = lambda t: C.c_void_p(t.data_ptr())
+    for name, rows, kin, nout in (("dw1", 65536, 400, 400), ("dw0", 65536, 432, 400)):
+        X, G = rnd(rows, kin), rnd(rows, nout)
+        P = [torch.zeros(64, kin, nout, device="cuda") for _ in range(2)]
+        cp = [torch.zeros(64, nout, device="cuda") for _ in range(2)]
+        sl = C.c_int(0)
+        fns = [lambda f=f: lab.lab_x3_dw_form(f, kin, nout, C.c_int64(rows), p(X), C.c_int64(kin), p(G), C.c_int64(nout),
+                                              p(P[f]), C.c_int64(nout), p(cp[f]), C.byref(sl), C.c_void_p(st)) for f in (0, 1)]
+        for fn in fns:
+            assert fn() == 0
+        torch.cuda.synchronize()
+        best = [1e9, 1e9]
+        for _ in range(args.rounds):
+            for f in (0, 1):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                for _i in range(args.iters):
+                    fns[f]()
+                b.record()
+                torch.cuda.synchronize()
+                best[f] = min(best[f], a.elapsed_time(b) / args.iters * 1e3)
+        ref = X.double().t() @ G.double()
+        mag = X.double().abs().t() @ G.double().abs()
+        err = [float(((P[f][: sl.value].double().sum(0) - ref).abs() / mag).max()) for f in (0, 1)]
+        same = torch.equal(P[0][: sl.value], P[1][: sl.value]) and torch.equal(cp[0][: sl.value], cp[1][: sl.value])
+        print("%-4s kernel alone: form 0 %6.1f us | form 1 %6.1f us (x%.2f)  (%d slices)  max err / sum|a||b| %.2e / %.2e  "
+              "bit-identical=%s" % (name, best[0], best[1], best[0] / best[1], sl.value, err[0], err[1], same), flush=True)
+
+
 if __name__ == "__main__":
+    if "--dwab" in sys.argv:
+        sys.argv.remove("--dwab")
+        ap = argparse.ArgumentParser()
+        ap.add_argument("--iters", type=int, default=20)
+        ap.add_argument("--rounds", type=int, default=5)
+        ap.add_argument("--lib", default=os.path.join(HERE, "_build", "libx3lab.so"))
+        dwab_main(ap.parse_args())
+        sys.exit(0)
     if "--dwk" in sys.argv:
         sys.argv.remove("--dwk")
         ap = argparse.ArgumentParser()
