@@ -1247,6 +1247,42 @@ int rec_dcn_v2_train_step(const rec_dcn_v2_net* net, int64_t batch, const int64_
                           int32_t num_thresholds, float* loss_out, float* pred_out, int32_t* status, void* workspace,
                           size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * FFM: field-aware factorisation machine, models/rank/ffm/net.py:90-133 (FFM.forward).
+ * F = num_slots + num_dense fields, R = F * dim: each sample's feature cube E [F, R] holds the table rows
+ * W[id_s] (s < S) and the dense rows dense[b,k] * dense_w[k, :]; E[i, j*dim .. +dim) is field i's vector
+ * for partner field j.
+ *   y1[b] = sum_s W1[id_s] + sum_k dense[b,k] * dense_w_one[k]
+ *   y2[b] = sum_{i<j} <E[i, j, :], E[j, i, :]>
+ * Built for F <= 64 and dim <= 32 (REC_ESHAPE otherwise, before any launch).  An id outside [0, num_rows)
+ * ORs REC_FLAG_INDEX_OOB into status and reads as a zero row.  When row_stride % 4 == 0 the kernels may read a
+ * row's pad columns [R, round_up(R, 4)) (their values are ignored).
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+  int64_t batch;       /* B */
+  int32_t num_slots;   /* S  (26): sparse fields, one id each */
+  int32_t num_dense;   /* Dn (13): dense fields */
+  int32_t dim;         /* D  (9) */
+  int64_t num_rows;    /* N rows in W / W1 */
+  int32_t row_stride;  /* floats between consecutive rows of W (>= R; 352 for R 351) */
+  int32_t grad_stride; /* floats between consecutive rows of row_grad (>= R); the pad columns are written 0 */
+} rec_ffm_desc;
+
+/* ids [B,S] i64; dense [B,Dn]; W [N,row_stride]; W1 [N]; dense_w [Dn,R]; dense_w_one [Dn] -> y1, y2 [B] */
+int rec_ffm_fwd(const rec_ffm_desc* desc, const int64_t* ids, const float* dense, const float* W, const float* W1,
+                const float* dense_w, const float* dense_w_one, float* y1, float* y2, int32_t* status, void* stream);
+/* Backward for dz [B] = dloss/d(y1 + y2 + bias):
+ *   row_grad [B*S, grad_stride] — SelectedRows.value of `embedding`, unmerged, in position order:
+ *     row b*S+i = dE[i] with dE[i, j, :] = dz * E[j, i, :] (j != i) and dE[i, i, :] = 0;
+ *   d_dense_w [Dn,R] = sum_b dense[b,k] * dE_b[S+k],  d_dense_w_one [Dn] = sum_b dz[b] * dense[b,k] —
+ *     per-block partials folded in a fixed order (two runs are bit-identical).
+ * The SelectedRows value of `embedding_one` is dz[b] for every (b,s); it is not materialised (read dz through
+ * rec_grad_layout{S,0,0}, as for rec_deepfm_fm_bwd). */
+int rec_ffm_bwd_workspace_bytes(const rec_ffm_desc* desc, size_t* bytes);
+int rec_ffm_bwd(const rec_ffm_desc* desc, const int64_t* ids, const float* dense, const float* W,
+                const float* dense_w, const float* dz, float* row_grad, float* d_dense_w, float* d_dense_w_one,
+                void* workspace, size_t workspace_bytes, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,12 @@ class DeepFMDesc(C.Structure):
                 ("feat_stride", C.c_int64)]
 
 
+class FFMDesc(C.Structure):
+    """rec_ffm_desc (include/recengine.h)."""
+    _fields_ = [("batch", C.c_int64), ("num_slots", C.c_int32), ("num_dense", C.c_int32), ("dim", C.c_int32),
+                ("num_rows", C.c_int64), ("row_stride", C.c_int32), ("grad_stride", C.c_int32)]
+
+
 class DeepFMNet(C.Structure):
     """rec_deepfm_net (include/recengine.h): the model of rec_deepfm_train_step as pointers into caller-owned memory."""
     MAX_LINEAR = 8
@@ -177,6 +183,9 @@ SIGNATURES = {
     "rec_deepfm_fm_bwd_workspace_bytes": (C.c_int, [C.POINTER(DeepFMDesc), C.POINTER(_SZ)]),
     "rec_deepfm_fm_bwd": (C.c_int, [C.POINTER(DeepFMDesc)] + [_P] * 11 + [_SZ, _P]),
     "rec_deepfm_fm_bwd_sorted": (C.c_int, [C.POINTER(DeepFMDesc)] + [_P] * 12 + [_SZ, _P]),
+    "rec_ffm_fwd": (C.c_int, [C.POINTER(FFMDesc)] + [_P] * 10),
+    "rec_ffm_bwd_workspace_bytes": (C.c_int, [C.POINTER(FFMDesc), C.POINTER(_SZ)]),
+    "rec_ffm_bwd": (C.c_int, [C.POINTER(FFMDesc)] + [_P] * 9 + [_SZ, _P, _P]),
     "rec_dense_fold_fwd": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P]),
     "rec_dense_fold_bwd": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _I32, _P]),
     "rec_dense_fold_fwd_full": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P]),

@@ -163,6 +163,29 @@ inline int dispatch_row_shape(int D, int stride, F&& f) {
   return REC_ESHAPE;
 }
 
+// The same for the row kernels that also take wide rows (rec_segment_partials, rec_sparse_adam_rows,
+// rec_adam_rows_all): every shape above dispatches exactly as above; float4 rows of 257..1024 floats (FFM's F*D)
+// get LANES 128 / 256, which those kernels run as one 64-lane wave per row making LANES/64 column passes
+// (row_lanes / row_passes below).
+template <class F>
+inline int dispatch_row_shape_wide(int D, int stride, F&& f) {
+  const bool v4 = (D % 4 == 0) && (stride % 4 == 0);
+  if (v4 && D > 4 * 64 && D <= 4 * 256) {
+    if (D <= 4 * 128) return f(std::integral_constant<int, 4>{}, std::integral_constant<int, 128>{});
+    return f(std::integral_constant<int, 4>{}, std::integral_constant<int, 256>{});
+  }
+  if (D > 4 * 64 && D <= 4 * 256) {
+    set_error("emb_dim %d (stride %d) unsupported: rows wider than 256 floats need D%%4==0 and stride%%4==0", D,
+              stride);
+    return REC_ESHAPE;
+  }
+  return dispatch_row_shape(D, stride, static_cast<F&&>(f));
+}
+template <int LANES>
+constexpr int row_lanes() { return LANES > kWave ? kWave : LANES; }   // lanes that share one row
+template <int LANES>
+constexpr int row_passes() { return LANES / row_lanes<LANES>(); }      // column passes of those lanes
+
 // Fork / join events of a two-stream step schedule (csrc/deepfm_step.hip, csrc/din_step.hip): kStepEvents events per
 // (device, stream, side stream), created on first use and kept for the life of the process (defined in deepfm_step.hip).
 constexpr int kStepEvents = 4;

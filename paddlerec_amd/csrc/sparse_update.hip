@@ -283,7 +283,8 @@ __global__ __launch_bounds__(kBlock) void segment_partials_kernel(
     const int32_t* __restrict__ spos, const float* __restrict__ grad, rec_grad_layout gl,
     float* __restrict__ partials) {
   static_assert(kSegTile == 64, "one wave per tile");
-  constexpr int G = 64 / LANES;  // row groups per wave
+  constexpr int WL = row_lanes<LANES>();   // lanes per row (a row of more than 64 x VEC floats: several passes)
+  constexpr int G = 64 / WL;               // row groups per wave
   const int lane = threadIdx.x % 64;
   const int64_t tile = (int64_t)blockIdx.x * (kBlock / 64) + threadIdx.x / 64;
   const int U = n_uniq[0];
@@ -304,23 +305,27 @@ __global__ __launch_bounds__(kBlock) void segment_partials_kernel(
     }
     return lo;
   };
-  const int grp = lane / LANES, d0 = (lane % LANES) * VEC;
+  const int grp = lane / WL, dl = (lane % WL) * VEC;
   auto piece = [&](int a, int b, int slot) {
-    float g[VEC];
 #pragma unroll
-    for (int i = 0; i < VEC; ++i) g[i] = 0.f;
-    if (d0 < D)
-      for (int k = a + grp; k < b; k += G) {
-        float t[VEC];
-        vload<VEC>(t, grad + grad_at(gl, spos, k, D) + d0);
+    for (int pass = 0; pass < row_passes<LANES>(); ++pass) {
+      const int d0 = dl + pass * WL * VEC;
+      float g[VEC];
 #pragma unroll
-        for (int i = 0; i < VEC; ++i) g[i] += t[i];
-      }
+      for (int i = 0; i < VEC; ++i) g[i] = 0.f;
+      if (d0 < D)
+        for (int k = a + grp; k < b; k += G) {
+          float t[VEC];
+          vload<VEC>(t, grad + grad_at(gl, spos, k, D) + d0);
 #pragma unroll
-    for (int off = LANES; off < 64; off <<= 1)
+          for (int i = 0; i < VEC; ++i) g[i] += t[i];
+        }
 #pragma unroll
-      for (int i = 0; i < VEC; ++i) g[i] += __shfl_xor(g[i], off, 64);
-    if (grp == 0 && d0 < D) vstore<VEC>(partials + (tile * 2 + slot) * D + d0, g);
+      for (int off = WL; off < 64; off <<= 1)
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) g[i] += __shfl_xor(g[i], off, 64);
+      if (grp == 0 && d0 < D) vstore<VEC>(partials + (tile * 2 + slot) * D + d0, g);
+    }
   };
   const int u0 = find(s);
   const int b0 = seg_off[u0], e0 = seg_off[u0 + 1];
@@ -409,30 +414,36 @@ __global__ __launch_bounds__(kBlock) void sparse_adam_rows_kernel(
     const float* __restrict__ grad, rec_grad_layout gl, const float* __restrict__ grad_scale,
     float* __restrict__ P, float* __restrict__ M, float* __restrict__ V, float lr_t, float eps_t,
     float b1, float b2) {
-  const int64_t u = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / LANES;
-  const int d0 = (threadIdx.x % LANES) * VEC;
-  if (u >= n_uniq[0] || d0 >= D) return;
+  constexpr int WL = row_lanes<LANES>();
+  const int64_t u = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / WL;
+  const int dl = (threadIdx.x % WL) * VEC;
+  if (u >= n_uniq[0] || dl >= D) return;
   const int64_t row = uniq[u];
   const int beg = seg_off[u], end = seg_off[u + 1];
-  float p[VEC], m[VEC], v[VEC], g[VEC];
-  const int64_t ro = row * stride + d0;
-  const int64_t so = row * sstride + d0;
-  vload<VEC>(p, P + ro);
-  vload<VEC>(m, M + so);
-  vload<VEC>(v, V + so);
 #pragma unroll
-  for (int i = 0; i < VEC; ++i) g[i] = 0.f;
-  segment_sum<VEC>(g, beg, end, spos, grad, gl, D, d0);
-  if (grad_scale) {   // global-norm clipping factor (device scalar)
-    const float sc = grad_scale[0];
+  for (int pass = 0; pass < row_passes<LANES>(); ++pass) {
+    const int d0 = dl + pass * WL * VEC;
+    if (pass > 0 && d0 >= D) return;
+    float p[VEC], m[VEC], v[VEC], g[VEC];
+    const int64_t ro = row * stride + d0;
+    const int64_t so = row * sstride + d0;
+    vload<VEC>(p, P + ro);
+    vload<VEC>(m, M + so);
+    vload<VEC>(v, V + so);
 #pragma unroll
-    for (int i = 0; i < VEC; ++i) g[i] = scale_grad(g[i], sc);
+    for (int i = 0; i < VEC; ++i) g[i] = 0.f;
+    segment_sum<VEC>(g, beg, end, spos, grad, gl, D, d0);
+    if (grad_scale) {   // global-norm clipping factor (device scalar)
+      const float sc = grad_scale[0];
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) g[i] = scale_grad(g[i], sc);
+    }
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) adam_elem(p[i], m[i], v[i], g[i], lr_t, eps_t, b1, b2);
+    vstore<VEC>(P + ro, p);
+    vstore<VEC>(M + so, m);
+    vstore<VEC>(V + so, v);
   }
-#pragma unroll
-  for (int i = 0; i < VEC; ++i) adam_elem(p[i], m[i], v[i], g[i], lr_t, eps_t, b1, b2);
-  vstore<VEC>(P + ro, p);
-  vstore<VEC>(M + so, m);
-  vstore<VEC>(V + so, v);
 }
 
 // ------------------------------------------------------------- narrow rows: one LANE per touched row
@@ -631,7 +642,8 @@ __global__ __launch_bounds__(kBlock) void adam_rows_all_kernel(
     const int32_t* __restrict__ spos, const float* __restrict__ grad, rec_grad_layout gl,
     const float* __restrict__ grad_scale, float* __restrict__ P, float* __restrict__ M,
     float* __restrict__ V, float lr_t, float eps_t, float b1, float b2) {
-  constexpr int RB = kBlock / LANES;
+  constexpr int WL = row_lanes<LANES>();
+  constexpr int RB = kBlock / WL;
   __shared__ int slot[RB];
   __shared__ int range[2];
   const int64_t r0 = (int64_t)blockIdx.x * RB;
@@ -648,31 +660,36 @@ __global__ __launch_bounds__(kBlock) void adam_rows_all_kernel(
   __syncthreads();
   for (int u = range[0] + threadIdx.x; u < range[1]; u += kBlock) slot[(int)(uniq[u] - r0)] = u;
   __syncthreads();
-  const int lr_ = threadIdx.x / LANES;
+  const int lr_ = threadIdx.x / WL;
   const int64_t row = r0 + lr_;
-  const int d0 = (threadIdx.x % LANES) * VEC;
-  if (row >= N || d0 >= D) return;
-  float p[VEC], m[VEC], v[VEC], g[VEC];
-  const int64_t ro = row * stride + d0, so = row * sstride + d0;
-  vload<VEC>(p, P + ro);
-  vload<VEC>(m, M + so);
-  vload<VEC>(v, V + so);
+  const int dl = (threadIdx.x % WL) * VEC;
+  if (row >= N || dl >= D) return;
 #pragma unroll
-  for (int i = 0; i < VEC; ++i) g[i] = 0.f;
-  const int u = slot[lr_];
-  if (u >= 0) {
-    segment_sum<VEC>(g, seg_off[u], seg_off[u + 1], spos, grad, gl, D, d0);
-    if (grad_scale) {
-      const float sc = grad_scale[0];
+  for (int pass = 0; pass < row_passes<LANES>(); ++pass) {
+    const int d0 = dl + pass * WL * VEC;
+    if (pass > 0 && d0 >= D) return;
+    float p[VEC], m[VEC], v[VEC], g[VEC];
+    const int64_t ro = row * stride + d0, so = row * sstride + d0;
+    vload<VEC>(p, P + ro);
+    vload<VEC>(m, M + so);
+    vload<VEC>(v, V + so);
 #pragma unroll
-      for (int i = 0; i < VEC; ++i) g[i] *= sc;
+    for (int i = 0; i < VEC; ++i) g[i] = 0.f;
+    const int u = slot[lr_];
+    if (u >= 0) {
+      segment_sum<VEC>(g, seg_off[u], seg_off[u + 1], spos, grad, gl, D, d0);
+      if (grad_scale) {
+        const float sc = grad_scale[0];
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) g[i] *= sc;
+      }
     }
-  }
 #pragma unroll
-  for (int i = 0; i < VEC; ++i) adam_elem(p[i], m[i], v[i], g[i], lr_t, eps_t, b1, b2);
-  vstore<VEC>(P + ro, p);
-  vstore<VEC>(M + so, m);
-  vstore<VEC>(V + so, v);
+    for (int i = 0; i < VEC; ++i) adam_elem(p[i], m[i], v[i], g[i], lr_t, eps_t, b1, b2);
+    vstore<VEC>(P + ro, p);
+    vstore<VEC>(M + so, m);
+    vstore<VEC>(V + so, v);
+  }
 }
 
 // The same on the record layout of sparse_adam_record_kernel — rec [N, stride] = W(D) | W1 | m1 | v1 | pad, MV [N, sstride] =
@@ -1777,7 +1794,7 @@ extern "C" int rec_segment_partials(int64_t n_max, int32_t emb_dim, const int32_
   if (n_max == 0) return REC_OK;
   REC_REQUIRE(((uintptr_t)partials) % 16 == 0, REC_EINVAL, "partials must be 16-byte aligned");
   const bool gvec = ((uintptr_t)grad) % 16 == 0 && (gl.group <= 0 || gl.group_stride % 4 == 0);
-  return dispatch_row_shape(emb_dim, gvec ? 4 : 1, [&](auto vec, auto lanes) -> int {
+  return dispatch_row_shape_wide(emb_dim, gvec ? 4 : 1, [&](auto vec, auto lanes) -> int {
     constexpr int VEC = decltype(vec)::value, LANES = decltype(lanes)::value;
     const int64_t tiles = (n_max + kSegTile - 1) / kSegTile;
     const int64_t grid = (tiles + kBlock / 64 - 1) / (kBlock / 64);
@@ -1834,10 +1851,10 @@ extern "C" int rec_sparse_adam_rows(int64_t n_max, int32_t emb_dim, int32_t row_
 #undef REC_NARROW
     return check_launch("rec_sparse_adam_rows (narrow)");
   }
-  return dispatch_row_shape(emb_dim, (gvec && state_stride % 4 == 0) ? row_stride : row_stride | 1,
-                            [&](auto vec, auto lanes) -> int {
+  return dispatch_row_shape_wide(emb_dim, (gvec && state_stride % 4 == 0) ? row_stride : row_stride | 1,
+                                 [&](auto vec, auto lanes) -> int {
     constexpr int VEC = decltype(vec)::value, LANES = decltype(lanes)::value;
-    const int64_t grid = (n_max * LANES + kBlock - 1) / kBlock;
+    const int64_t grid = (n_max * row_lanes<LANES>() + kBlock - 1) / kBlock;
     REC_REQUIRE(grid < (1ll << 31), REC_ESHAPE, "too many rows");
     hipLaunchKernelGGL((sparse_adam_rows_kernel<VEC, LANES>), dim3((unsigned)grid), dim3(kBlock),
                        0, st, emb_dim, row_stride, state_stride, n_uniq, uniq_rows, seg_offset, sorted_pos, grad,
@@ -2316,9 +2333,9 @@ extern "C" int rec_adam_rows_all(int64_t num_rows, int32_t emb_dim, int32_t row_
   adam_scalars(hyper, &lr_t, &eps_t);
   const bool gvec = ((uintptr_t)grad) % 16 == 0 && (gl.group <= 0 || gl.group_stride % 4 == 0) &&
                     state_stride % 4 == 0;
-  return dispatch_row_shape(emb_dim, gvec ? row_stride : row_stride | 1, [&](auto vec, auto lanes) -> int {
+  return dispatch_row_shape_wide(emb_dim, gvec ? row_stride : row_stride | 1, [&](auto vec, auto lanes) -> int {
     constexpr int VEC = decltype(vec)::value, LANES = decltype(lanes)::value;
-    constexpr int RB = kBlock / LANES;
+    constexpr int RB = kBlock / row_lanes<LANES>();
     const int64_t grid = (num_rows + RB - 1) / RB;
     REC_REQUIRE(grid < (1ll << 31), REC_ESHAPE, "too many rows");
     hipLaunchKernelGGL((adam_rows_all_kernel<VEC, LANES>), dim3((unsigned)grid), dim3(kBlock), 0,

@@ -10,7 +10,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import (EPI, AdagradHyper, AdamHyper, CinView, DeepFMDesc, DinDesc, GemmBImage, GemmDesc, GemmEpilogueArgs, GradLayout,
+from ._lib import (EPI, AdagradHyper, AdamHyper, CinView, DeepFMDesc, DinDesc, FFMDesc, GemmBImage, GemmDesc, GemmEpilogueArgs, GradLayout,
                    GradSrc, LazyInit, MultislotDesc, PsAccessor, PsLayout, RecError, check)
 
 _recorder = None        # paddlerec_amd.plan.CallPlan while a step is being recorded
@@ -323,6 +323,82 @@ def deepfm_fm_bwd(dense, feat, sum_emb, d_feat_dnn, dy1, dy2, S, ws, out=None, d
                                   _p(dy1), _p(dy2), _p(dense_w), _p(row_grad), _p(d_dense_w),
                                   _p(d_dense_w_one),
                                   _p(w), C.c_size_t(w.numel()), _stream()), "rec_deepfm_fm_bwd")
+    return row_grad, d_dense_w, d_dense_w_one
+
+
+# ------------------------------------------------------------------ FFM field-aware interaction
+def _ffm_desc(ids, dense, dim, W, what):
+    _chk(ids, torch.int64, "ids")
+    if ids.dim() != 2:
+        raise RecError("%s: ids must be [B, S]" % what)
+    B, S = ids.shape
+    _chk(dense, torch.float32, "dense")
+    if dense.dim() != 2 or dense.shape[0] != B:
+        raise RecError("%s: dense must be [B, Dn]" % what)
+    Dn = dense.shape[1]
+    width, stride = _chk_table(W, "W")
+    R = (S + Dn) * int(dim)
+    if width < R:
+        raise RecError("%s: W rows hold %d floats, fields x dim = %d" % (what, width, R))
+    return B, S, Dn, R, stride
+
+
+def ffm_fwd(ids, dense, W, W1, dense_w, dense_w_one, dim, status=None, out=None):
+    """ids [B,S] i64, dense [B,Dn] f32, W [N, >= R] (R = (S+Dn)*dim; a padded row stride is fine), W1 [N,1]|[N],
+    dense_w [Dn,R]|[1,Dn,R], dense_w_one [Dn] -> y1 [B,1], y2 [B,1], status  (rec_ffm_fwd)."""
+    B, S, Dn, R, stride = _ffm_desc(ids, dense, dim, W, "ffm_fwd")
+    N = W.shape[0]
+    _chk(W1, torch.float32, "W1")
+    _chk(dense_w, torch.float32, "dense_w")
+    _chk(dense_w_one, torch.float32, "dense_w_one", (Dn,))
+    if W1.numel() != N or dense_w.numel() != Dn * R:
+        raise RecError("ffm_fwd: W1 / dense_w shape mismatch")
+    dev = ids.device
+    if out is None:
+        y1 = torch.empty(B, 1, dtype=torch.float32, device=dev)
+        y2 = torch.empty(B, 1, dtype=torch.float32, device=dev)
+    else:
+        y1, y2 = out
+        _chk(y1, torch.float32, "y1")
+        _chk(y2, torch.float32, "y2")
+        if y1.numel() != B or y2.numel() != B:
+            raise RecError("ffm_fwd: y1 / y2 must hold B values")
+    if status is None:
+        status = new_status(dev)
+    desc = FFMDesc(B, S, Dn, int(dim), N, stride, 0)
+    check(lib().rec_ffm_fwd(C.byref(desc), _p(ids), _p(dense), _p(W), _p(W1), _p(dense_w), _p(dense_w_one), _p(y1),
+                            _p(y2), _p(status), _stream()), "rec_ffm_fwd")
+    return y1, y2, status
+
+
+def ffm_bwd(ids, dense, W, dense_w, dz, dim, ws, out=None, status=None, grad_stride=None):
+    """dz [B] | [B,1] = dloss / dlogit -> row_grad [B*S, grad_stride] (default: R rounded up to 4 floats; the pad
+    columns are 0), d_dense_w [Dn,R], d_dense_w_one [Dn]  (rec_ffm_bwd).  The W1 gradient is dz itself, read with
+    grad_div = S by the row updates."""
+    B, S, Dn, R, stride = _ffm_desc(ids, dense, dim, W, "ffm_bwd")
+    _chk(dense_w, torch.float32, "dense_w")
+    _chk(dz, torch.float32, "dz")
+    if dense_w.numel() != Dn * R or dz.numel() != B:
+        raise RecError("ffm_bwd: dense_w / dz shape mismatch")
+    gs = int(grad_stride) if grad_stride else (R + 3) // 4 * 4
+    dev = ids.device
+    if out is None:
+        row_grad = torch.empty(B * S, gs, dtype=torch.float32, device=dev)
+        d_dense_w = torch.empty(Dn, R, dtype=torch.float32, device=dev)
+        d_dense_w_one = torch.empty(Dn, dtype=torch.float32, device=dev)
+    else:
+        row_grad, d_dense_w, d_dense_w_one = out
+    _chk(row_grad, torch.float32, "row_grad", (B * S, gs))
+    _chk(d_dense_w, torch.float32, "d_dense_w")
+    _chk(d_dense_w_one, torch.float32, "d_dense_w_one", (Dn,))
+    if d_dense_w.numel() != Dn * R:
+        raise RecError("ffm_bwd: d_dense_w must hold Dn x R floats")
+    desc = FFMDesc(B, S, Dn, int(dim), W.shape[0], stride, gs)
+    nbytes = C.c_size_t(0)
+    check(lib().rec_ffm_bwd_workspace_bytes(C.byref(desc), C.byref(nbytes)), "rec_ffm_bwd_workspace_bytes")
+    w = ws.get(nbytes.value)
+    check(lib().rec_ffm_bwd(C.byref(desc), _p(ids), _p(dense), _p(W), _p(dense_w), _p(dz), _p(row_grad), _p(d_dense_w),
+                            _p(d_dense_w_one), _p(w), C.c_size_t(w.numel()), _p(status), _stream()), "rec_ffm_bwd")
     return row_grad, d_dense_w, d_dense_w_one
 
 
