@@ -322,6 +322,14 @@ int rec_sparse_adam_rows(int64_t n_max, int32_t emb_dim, int32_t row_stride,
                          const rec_grad_layout* grad_layout, const float* grad_scale, float* P,
                          float* M, float* V, const rec_adam_hyper* hyper, void* stream);
 
+/* The same with paddle.regularizer.L2Decay(l2_coeff) on the parameter: the merged (and scaled) gradient of a touched row
+ * becomes g + l2_coeff * w before Adam.  l2_coeff == 0 runs the kernels of rec_sparse_adam_rows. */
+int rec_sparse_adam_rows_l2(int64_t n_max, int32_t emb_dim, int32_t row_stride, int32_t state_stride,
+                            const int32_t* n_uniq, const int64_t* uniq_rows, const int32_t* seg_offset,
+                            const int32_t* sorted_pos, const float* grad, const rec_grad_layout* grad_layout,
+                            const float* grad_scale, float* P, float* M, float* V, const rec_adam_hyper* hyper,
+                            float l2_coeff, void* stream);
+
 /* Both embeddings of a DeepFM row (deepfm/net.py:62-86: `embedding` [N,D] and `embedding_one` [N,1]) in one
  * pass over the record layout  rec [N, rec_stride] = W(D) | W1 | m1 | v1 | pad,  MV [N, state_stride] = m(D) at
  * 0 | v(D) at v_offset:  W/m/v from (grad, grad_layout), W1/m1/v1 from (grad1, grad1_layout) — for DeepFM
@@ -499,6 +507,14 @@ int rec_adam_rows_all(int64_t num_rows, int32_t emb_dim, int32_t row_stride, int
                       const int32_t* sorted_pos, const float* grad, const rec_grad_layout* grad_layout,
                       const float* grad_scale, float* P, float* M, float* V, const rec_adam_hyper* hyper,
                       void* stream);
+
+/* The same with L2Decay(l2_coeff): every row moves with g + l2_coeff * w (g = 0 for rows absent from the gradient).
+ * l2_coeff == 0 runs the kernels of rec_adam_rows_all. */
+int rec_adam_rows_all_l2(int64_t num_rows, int32_t emb_dim, int32_t row_stride, int32_t state_stride,
+                         const int32_t* n_uniq, const int64_t* uniq_rows, const int32_t* seg_offset,
+                         const int32_t* sorted_pos, const float* grad, const rec_grad_layout* grad_layout,
+                         const float* grad_scale, float* P, float* M, float* V, const rec_adam_hyper* hyper,
+                         float l2_coeff, void* stream);
 
 /* The same on the record layout of rec_sparse_adam_record (rec = W(D) | W1 | m1 | v1 | pad, MV = m(D) | v(D) at v_offset):
  * both embeddings of every row in ONE pass — 512 B per row where two rec_adam_rows_all passes move 768 (the second
@@ -1282,6 +1298,52 @@ int rec_ffm_bwd_workspace_bytes(const rec_ffm_desc* desc, size_t* bytes);
 int rec_ffm_bwd(const rec_ffm_desc* desc, const int64_t* ids, const float* dense, const float* W,
                 const float* dense_w, const float* dz, float* row_grad, float* d_dense_w, float* d_dense_w_one,
                 void* workspace, size_t workspace_bytes, int32_t* status, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * FEFM: field-embedded factorisation machine, models/rank/deepfefm/net.py:118-187 (FEFM.forward).
+ * F = num_slots + num_dense fields, P = F (F - 1) / 2 pairs p = (i, j), i < j, in itertools.combinations order.
+ *   id[b,f]   = ids[b,f] (f < S),  int64(dense[b,f-S] * 1e5 + 1e6 + 2) (f >= S: three rounded f32 operations, truncated)
+ *   x[b,f,:]  = W[id[b,f], 0:dim]   (0 where id == 0: padding_idx)
+ *   y1[b]     = sum_{f<S} W1[id[b,f]] (0 where id == 0) + sum_k dense[b,k] * dense_w_one[k]
+ *   t[b,p]    = x[b,i,:]^T (FE_p + FE_p^T) x[b,j,:],   y2[b] = sum_p t[b,p]
+ *   dnn_in[b] = [ x[b, 0:S, :] (S*dim) | dense[b,:] * dense_w_one (Dn) | t[b,:] (P) ]   at row stride ld
+ * Built for 2 <= F <= 64, dim <= 64, num_rows < 2^31 (REC_ESHAPE otherwise, before any launch).  An id outside
+ * [0, num_rows) — a derived one included: negative, huge or NaN dense values — ORs REC_FLAG_INDEX_OOB into status and
+ * reads as a zero row; it never indexes memory.  Exact f32.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+  int64_t batch;       /* B */
+  int32_t num_slots;   /* S  (26): sparse fields, one id each */
+  int32_t num_dense;   /* Dn (13): dense fields, looked up in W through the derived id */
+  int32_t dim;         /* D  (9 / 48) */
+  int64_t num_rows;    /* N rows in W / W1 */
+  int32_t row_stride;  /* floats between consecutive rows of W (>= D) */
+  int32_t grad_stride; /* floats between consecutive rows of row_grad (>= D); the pad columns are written 0 */
+  int64_t ld;          /* floats between consecutive rows of dnn_in / d_dnn_in (>= S*D + Dn + P) */
+} rec_fefm_desc;
+
+/* ids [B,S] i64; dense [B,Dn]; W [N,row_stride]; W1 [N]; dense_w_one [Dn]; FE [P,D,D] -> y1, y2 [B], dnn_in [B,ld] (the
+ * three column groups, written in place), ids_all [B,F] i64 (the merge keys of the table gradient; -1 for a dense value
+ * whose id is not a finite number).  workspace: rec_fefm_fwd_workspace_bytes (the symmetrised matrices, and the y2
+ * partials of the blocks that share a tile when the batch has fewer tiles than the chip has CUs). */
+int rec_fefm_fwd_workspace_bytes(const rec_fefm_desc* desc, size_t* bytes);
+int rec_fefm_fwd(const rec_fefm_desc* desc, const int64_t* ids, const float* dense, const float* W, const float* W1,
+                 const float* dense_w_one, const float* FE, float* y1, float* y2, float* dnn_in, int64_t* ids_all,
+                 void* workspace, size_t workspace_bytes, int32_t* status, void* stream);
+/* Backward for dz [B] = dloss / d(y1 + y2 + y_dnn) and d_dnn_in [B,ld] = dloss / d dnn_in;
+ * g[b,p] = dz[b] + d_dnn_in[b, S*D + Dn + p]:
+ *   row_grad [B*F, grad_stride] — SelectedRows.value of `embedding`, unmerged, in position order b*F + f:
+ *     dx[b,i,:] = sum_{j != i} g[b,p(i,j)] (FE_p + FE_p^T) x[b,j,:]  (+ d_dnn_in[b, i*D .. (i+1)*D) for i < S);
+ *     rows of padding positions (id == 0) and the pad columns are 0;
+ *   d_dense_w_one [Dn] = sum_b (dz[b] + d_dnn_in[b, S*D + k]) * dense[b,k];
+ *   d_FE [P,D,D] = sum_b g[b,p] (x_i x_j^T + x_j x_i^T), or NULL: that work is skipped.
+ * Both batch sums are per-block partials folded in a fixed order (two runs are bit-identical).  The SelectedRows value
+ * of `embedding_one` is dz[b] for the S sparse positions of a sample (rec_grad_layout{S,0,0} over a grouping of ids
+ * [B,S]); it is not materialised. */
+int rec_fefm_bwd_workspace_bytes(const rec_fefm_desc* desc, int32_t want_d_fe, size_t* bytes);
+int rec_fefm_bwd(const rec_fefm_desc* desc, const int64_t* ids_all, const float* dense, const float* W, const float* FE,
+                 const float* dz, const float* d_dnn_in, float* row_grad, float* d_dense_w_one, float* d_FE,
+                 void* workspace, size_t workspace_bytes, int32_t* status, void* stream);
 
 #ifdef __cplusplus
 }

@@ -29,6 +29,12 @@ class FFMDesc(C.Structure):
                 ("num_rows", C.c_int64), ("row_stride", C.c_int32), ("grad_stride", C.c_int32)]
 
 
+class FEFMDesc(C.Structure):
+    """rec_fefm_desc (include/recengine.h)."""
+    _fields_ = [("batch", C.c_int64), ("num_slots", C.c_int32), ("num_dense", C.c_int32), ("dim", C.c_int32),
+                ("num_rows", C.c_int64), ("row_stride", C.c_int32), ("grad_stride", C.c_int32), ("ld", C.c_int64)]
+
+
 class DeepFMNet(C.Structure):
     """rec_deepfm_net (include/recengine.h): the model of rec_deepfm_train_step as pointers into caller-owned memory."""
     MAX_LINEAR = 8
@@ -186,6 +192,10 @@ SIGNATURES = {
     "rec_ffm_fwd": (C.c_int, [C.POINTER(FFMDesc)] + [_P] * 10),
     "rec_ffm_bwd_workspace_bytes": (C.c_int, [C.POINTER(FFMDesc), C.POINTER(_SZ)]),
     "rec_ffm_bwd": (C.c_int, [C.POINTER(FFMDesc)] + [_P] * 9 + [_SZ, _P, _P]),
+    "rec_fefm_fwd_workspace_bytes": (C.c_int, [C.POINTER(FEFMDesc), C.POINTER(_SZ)]),
+    "rec_fefm_fwd": (C.c_int, [C.POINTER(FEFMDesc)] + [_P] * 11 + [_SZ, _P, _P]),
+    "rec_fefm_bwd_workspace_bytes": (C.c_int, [C.POINTER(FEFMDesc), _I32, C.POINTER(_SZ)]),
+    "rec_fefm_bwd": (C.c_int, [C.POINTER(FEFMDesc)] + [_P] * 10 + [_SZ, _P, _P]),
     "rec_dense_fold_fwd": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P]),
     "rec_dense_fold_bwd": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _I32, _P]),
     "rec_dense_fold_fwd_full": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P]),
@@ -203,6 +213,8 @@ SIGNATURES = {
     "rec_segment_partials": (C.c_int, [_I64, _I32, _P, _P, _P, _P, C.POINTER(GradLayout), _P, _P]),
     "rec_sparse_adam_rows": (C.c_int, [_I64, _I32, _I32, _I32, _P, _P, _P, _P, _P, C.POINTER(GradLayout), _P,
                                        _P, _P, _P, C.POINTER(AdamHyper), _P]),
+    "rec_sparse_adam_rows_l2": (C.c_int, [_I64, _I32, _I32, _I32, _P, _P, _P, _P, _P, C.POINTER(GradLayout), _P,
+                                          _P, _P, _P, C.POINTER(AdamHyper), _F, _P]),
     "rec_sparse_adam_record": (C.c_int, [_I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, C.POINTER(GradLayout), _P,
                                          C.POINTER(GradLayout), _P, _P, _P, C.POINTER(AdamHyper), _P]),
     "rec_adam_record_all": (C.c_int, [_I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, C.POINTER(GradLayout), _P,
@@ -232,6 +244,8 @@ SIGNATURES = {
                                           _P, C.POINTER(AdagradHyper), _P]),
     "rec_adam_rows_all": (C.c_int, [_I64, _I32, _I32, _I32, _P, _P, _P, _P, _P, C.POINTER(GradLayout), _P,
                                     _P, _P, _P, C.POINTER(AdamHyper), _P]),
+    "rec_adam_rows_all_l2": (C.c_int, [_I64, _I32, _I32, _I32, _P, _P, _P, _P, _P, C.POINTER(GradLayout), _P,
+                                       _P, _P, _P, C.POINTER(AdamHyper), _F, _P]),
     "rec_adam_dense": (C.c_int, [_I64, _P, _P, _P, _P, _P, C.POINTER(AdamHyper), _P]),
     "rec_sumsq_workspace_bytes": (C.c_int, [C.POINTER(_SZ)]),
     "rec_sumsq": (C.c_int, [_I64, _P, _P, _I32, _P, _SZ, _P]),

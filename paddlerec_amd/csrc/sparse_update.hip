@@ -392,6 +392,13 @@ __device__ __forceinline__ float scale_grad(float g, float sc) {
   return g * sc;
 }
 
+// L2Decay appended to a row gradient (paddle.regularizer.L2Decay: g + coeff * w), two rounded operations
+__device__ __forceinline__ float l2_grad(float g, float coeff, float w) {
+#pragma clang fp contract(off)
+  const float d = coeff * w;
+  return g + d;
+}
+
 __device__ __forceinline__ void adam_elem(float& p, float& m, float& v, float g, float lr_t, float eps_t,
                                           float b1, float b2) {
 #pragma clang fp contract(off)
@@ -407,13 +414,14 @@ __device__ __forceinline__ void adam_elem(float& p, float& m, float& v, float g,
 }
 
 // --------------------------------------------------------------------------- lazy sparse Adam
-template <int VEC, int LANES>
+// L2 (rec_sparse_adam_rows_l2): g + l2 * w on the merged gradient; L2 = false is the kernel of rec_sparse_adam_rows
+template <int VEC, int LANES, bool L2 = false>
 __global__ __launch_bounds__(kBlock) void sparse_adam_rows_kernel(
     int D, int stride, int sstride, const int32_t* __restrict__ n_uniq, const int64_t* __restrict__ uniq,
     const int32_t* __restrict__ seg_off, const int32_t* __restrict__ spos,
     const float* __restrict__ grad, rec_grad_layout gl, const float* __restrict__ grad_scale,
     float* __restrict__ P, float* __restrict__ M, float* __restrict__ V, float lr_t, float eps_t,
-    float b1, float b2) {
+    float b1, float b2, float l2 = 0.f) {
   constexpr int WL = row_lanes<LANES>();
   const int64_t u = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / WL;
   const int dl = (threadIdx.x % WL) * VEC;
@@ -437,6 +445,10 @@ __global__ __launch_bounds__(kBlock) void sparse_adam_rows_kernel(
       const float sc = grad_scale[0];
 #pragma unroll
       for (int i = 0; i < VEC; ++i) g[i] = scale_grad(g[i], sc);
+    }
+    if constexpr (L2) {
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) g[i] = l2_grad(g[i], l2, p[i]);
     }
 #pragma unroll
     for (int i = 0; i < VEC; ++i) adam_elem(p[i], m[i], v[i], g[i], lr_t, eps_t, b1, b2);
@@ -534,13 +546,13 @@ __device__ __forceinline__ void narrow_segment_sum(float (&g)[NV * 4], int beg, 
   }
 }
 
-template <int NV, bool V4>
+template <int NV, bool V4, bool L2 = false>
 __global__ __launch_bounds__(kBlock) void sparse_adam_rows_narrow_kernel(
     int D, int stride, int sstride, const int32_t* __restrict__ n_uniq, const int64_t* __restrict__ uniq,
     const int32_t* __restrict__ seg_off, const int32_t* __restrict__ spos,
     const float* __restrict__ grad, rec_grad_layout gl, const float* __restrict__ grad_scale,
     float* __restrict__ P, float* __restrict__ M, float* __restrict__ V, float lr_t, float eps_t,
-    float b1, float b2) {
+    float b1, float b2, float l2 = 0.f) {
   // the launch is sized for n_max (a capacity: the number of distinct rows is only known on the device), so the
   // grid is capped at a few resident rounds and strides over the rows that exist
   const int nu = n_uniq[0];
@@ -559,6 +571,7 @@ __global__ __launch_bounds__(kBlock) void sparse_adam_rows_narrow_kernel(
   for (int d = 0; d < NV * 4; ++d) {
     if (d < D) {
       if (grad_scale) g[d] = scale_grad(g[d], sc);
+      if constexpr (L2) g[d] = l2_grad(g[d], l2, p[d]);
       adam_elem(p[d], m[d], v[d], g[d], lr_t, eps_t, b1, b2);
     }
   }
@@ -635,13 +648,13 @@ __global__ __launch_bounds__(kBlock) void sparse_adam_record_kernel(
 // from the merged gradient use g = 0.  One pass over the whole table (6*N*D*4 B of traffic — the reason the
 // engine defaults to the lazy variant); a block owns kBlock/LANES consecutive rows, finds the slice of the
 // sorted unique-row list that falls inside with two binary searches and spreads it into an LDS slot map.
-template <int VEC, int LANES>
+template <int VEC, int LANES, bool L2 = false>
 __global__ __launch_bounds__(kBlock) void adam_rows_all_kernel(
     int64_t N, int D, int stride, int sstride, const int32_t* __restrict__ n_uniq,
     const int64_t* __restrict__ uniq, const int32_t* __restrict__ seg_off,
     const int32_t* __restrict__ spos, const float* __restrict__ grad, rec_grad_layout gl,
     const float* __restrict__ grad_scale, float* __restrict__ P, float* __restrict__ M,
-    float* __restrict__ V, float lr_t, float eps_t, float b1, float b2) {
+    float* __restrict__ V, float lr_t, float eps_t, float b1, float b2, float l2 = 0.f) {
   constexpr int WL = row_lanes<LANES>();
   constexpr int RB = kBlock / WL;
   __shared__ int slot[RB];
@@ -683,6 +696,10 @@ __global__ __launch_bounds__(kBlock) void adam_rows_all_kernel(
 #pragma unroll
         for (int i = 0; i < VEC; ++i) g[i] *= sc;
       }
+    }
+    if constexpr (L2) {
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) g[i] = l2_grad(g[i], l2, p[i]);
     }
 #pragma unroll
     for (int i = 0; i < VEC; ++i) adam_elem(p[i], m[i], v[i], g[i], lr_t, eps_t, b1, b2);
@@ -1805,12 +1822,13 @@ extern "C" int rec_segment_partials(int64_t n_max, int32_t emb_dim, const int32_
   });
 }
 
-extern "C" int rec_sparse_adam_rows(int64_t n_max, int32_t emb_dim, int32_t row_stride,
-                                    int32_t state_stride, const int32_t* n_uniq, const int64_t* uniq_rows,
-                                    const int32_t* seg_offset, const int32_t* sorted_pos,
-                                    const float* grad, const rec_grad_layout* grad_layout,
-                                    const float* grad_scale, float* P, float* M, float* V,
-                                    const rec_adam_hyper* hyper, void* stream) {
+// rec_sparse_adam_rows (l2 == 0: the kernels without the decay term, as before) and rec_sparse_adam_rows_l2
+static int sparse_adam_rows_impl(int64_t n_max, int32_t emb_dim, int32_t row_stride,
+                                 int32_t state_stride, const int32_t* n_uniq, const int64_t* uniq_rows,
+                                 const int32_t* seg_offset, const int32_t* sorted_pos,
+                                 const float* grad, const rec_grad_layout* grad_layout,
+                                 const float* grad_scale, float* P, float* M, float* V,
+                                 const rec_adam_hyper* hyper, float l2, void* stream) {
   rec_grad_layout gl = {1, 0, 0, nullptr, nullptr};
   if (grad_layout) gl = *grad_layout;
   REC_REQUIRE(n_max >= 0 && emb_dim > 0 && row_stride >= emb_dim && gl.div >= 1, REC_EINVAL,
@@ -1837,10 +1855,14 @@ extern "C" int rec_sparse_adam_rows(int64_t n_max, int32_t emb_dim, int32_t row_
     int64_t grid = (n_max + kBlock - 1) / kBlock;
     if (grid > (int64_t)kNumCU * 32) grid = (int64_t)kNumCU * 32;   // grid-stride loop in the kernel
     const int nv = (emb_dim + 3) / 4;
-#define REC_NARROW(NV_, V4_)                                                                                 \
-  hipLaunchKernelGGL((sparse_adam_rows_narrow_kernel<NV_, V4_>), dim3((unsigned)grid), dim3(kBlock), 0, st,   \
-                     emb_dim, row_stride, state_stride, n_uniq, uniq_rows, seg_offset, sorted_pos, grad, gl,   \
-                     grad_scale, P, M, V, lr_t, eps_t, hyper->beta1, hyper->beta2)
+#define REC_NARROW_L2(NV_, V4_, L2_)                                                                          \
+  hipLaunchKernelGGL((sparse_adam_rows_narrow_kernel<NV_, V4_, L2_>), dim3((unsigned)grid), dim3(kBlock), 0, st, \
+                     emb_dim, row_stride, state_stride, n_uniq, uniq_rows, seg_offset, sorted_pos, grad, gl,      \
+                     grad_scale, P, M, V, lr_t, eps_t, hyper->beta1, hyper->beta2, l2)
+#define REC_NARROW(NV_, V4_)                                         \
+  do {                                                               \
+    if (l2 != 0.f) REC_NARROW_L2(NV_, V4_, true); else REC_NARROW_L2(NV_, V4_, false); \
+  } while (0)
     if (v4) {
       if (nv == 1) REC_NARROW(1, true); else if (nv == 2) REC_NARROW(2, true);
       else if (nv == 3) REC_NARROW(3, true); else REC_NARROW(4, true);
@@ -1849,6 +1871,7 @@ extern "C" int rec_sparse_adam_rows(int64_t n_max, int32_t emb_dim, int32_t row_
       else if (nv == 3) REC_NARROW(3, false); else REC_NARROW(4, false);
     }
 #undef REC_NARROW
+#undef REC_NARROW_L2
     return check_launch("rec_sparse_adam_rows (narrow)");
   }
   return dispatch_row_shape_wide(emb_dim, (gvec && state_stride % 4 == 0) ? row_stride : row_stride | 1,
@@ -1856,11 +1879,36 @@ extern "C" int rec_sparse_adam_rows(int64_t n_max, int32_t emb_dim, int32_t row_
     constexpr int VEC = decltype(vec)::value, LANES = decltype(lanes)::value;
     const int64_t grid = (n_max * row_lanes<LANES>() + kBlock - 1) / kBlock;
     REC_REQUIRE(grid < (1ll << 31), REC_ESHAPE, "too many rows");
-    hipLaunchKernelGGL((sparse_adam_rows_kernel<VEC, LANES>), dim3((unsigned)grid), dim3(kBlock),
-                       0, st, emb_dim, row_stride, state_stride, n_uniq, uniq_rows, seg_offset, sorted_pos, grad,
-                       gl, grad_scale, P, M, V, lr_t, eps_t, hyper->beta1, hyper->beta2);
+    if (l2 != 0.f)
+      hipLaunchKernelGGL((sparse_adam_rows_kernel<VEC, LANES, true>), dim3((unsigned)grid), dim3(kBlock),
+                         0, st, emb_dim, row_stride, state_stride, n_uniq, uniq_rows, seg_offset, sorted_pos, grad,
+                         gl, grad_scale, P, M, V, lr_t, eps_t, hyper->beta1, hyper->beta2, l2);
+    else
+      hipLaunchKernelGGL((sparse_adam_rows_kernel<VEC, LANES, false>), dim3((unsigned)grid), dim3(kBlock),
+                         0, st, emb_dim, row_stride, state_stride, n_uniq, uniq_rows, seg_offset, sorted_pos, grad,
+                         gl, grad_scale, P, M, V, lr_t, eps_t, hyper->beta1, hyper->beta2, 0.f);
     return check_launch("rec_sparse_adam_rows");
   });
+}
+
+extern "C" int rec_sparse_adam_rows(int64_t n_max, int32_t emb_dim, int32_t row_stride,
+                                    int32_t state_stride, const int32_t* n_uniq, const int64_t* uniq_rows,
+                                    const int32_t* seg_offset, const int32_t* sorted_pos,
+                                    const float* grad, const rec_grad_layout* grad_layout,
+                                    const float* grad_scale, float* P, float* M, float* V,
+                                    const rec_adam_hyper* hyper, void* stream) {
+  return sparse_adam_rows_impl(n_max, emb_dim, row_stride, state_stride, n_uniq, uniq_rows, seg_offset, sorted_pos,
+                               grad, grad_layout, grad_scale, P, M, V, hyper, 0.f, stream);
+}
+
+extern "C" int rec_sparse_adam_rows_l2(int64_t n_max, int32_t emb_dim, int32_t row_stride,
+                                       int32_t state_stride, const int32_t* n_uniq, const int64_t* uniq_rows,
+                                       const int32_t* seg_offset, const int32_t* sorted_pos,
+                                       const float* grad, const rec_grad_layout* grad_layout,
+                                       const float* grad_scale, float* P, float* M, float* V,
+                                       const rec_adam_hyper* hyper, float l2_coeff, void* stream) {
+  return sparse_adam_rows_impl(n_max, emb_dim, row_stride, state_stride, n_uniq, uniq_rows, seg_offset, sorted_pos,
+                               grad, grad_layout, grad_scale, P, M, V, hyper, l2_coeff, stream);
 }
 
 extern "C" int rec_sparse_adam_record(int64_t n_max, int32_t emb_dim, int32_t rec_stride,
@@ -2315,11 +2363,11 @@ extern "C" int rec_sgd_dense(int64_t n, float* p, const float* g, float lr, void
   return check_launch("rec_sgd_dense");
 }
 
-extern "C" int rec_adam_rows_all(int64_t num_rows, int32_t emb_dim, int32_t row_stride,
-                                 int32_t state_stride, const int32_t* n_uniq, const int64_t* uniq_rows,
-                                 const int32_t* seg_offset, const int32_t* sorted_pos, const float* grad,
-                                 const rec_grad_layout* grad_layout, const float* grad_scale, float* P,
-                                 float* M, float* V, const rec_adam_hyper* hyper, void* stream) {
+static int adam_rows_all_impl(int64_t num_rows, int32_t emb_dim, int32_t row_stride,
+                              int32_t state_stride, const int32_t* n_uniq, const int64_t* uniq_rows,
+                              const int32_t* seg_offset, const int32_t* sorted_pos, const float* grad,
+                              const rec_grad_layout* grad_layout, const float* grad_scale, float* P,
+                              float* M, float* V, const rec_adam_hyper* hyper, float l2, void* stream) {
   rec_grad_layout gl = {1, 0, 0, nullptr, nullptr};
   if (grad_layout) gl = *grad_layout;
   REC_REQUIRE(num_rows >= 0 && emb_dim > 0 && row_stride >= emb_dim && gl.div >= 1, REC_EINVAL, "bad sizes");
@@ -2338,10 +2386,34 @@ extern "C" int rec_adam_rows_all(int64_t num_rows, int32_t emb_dim, int32_t row_
     constexpr int RB = kBlock / row_lanes<LANES>();
     const int64_t grid = (num_rows + RB - 1) / RB;
     REC_REQUIRE(grid < (1ll << 31), REC_ESHAPE, "too many rows");
-    hipLaunchKernelGGL((adam_rows_all_kernel<VEC, LANES>), dim3((unsigned)grid), dim3(kBlock), 0,
-                       (hipStream_t)stream, num_rows, emb_dim, row_stride, state_stride, n_uniq, uniq_rows,
-                       seg_offset, sorted_pos, grad, gl, grad_scale, P, M, V, lr_t, eps_t, hyper->beta1,
-                       hyper->beta2);
+    if (l2 != 0.f)
+      hipLaunchKernelGGL((adam_rows_all_kernel<VEC, LANES, true>), dim3((unsigned)grid), dim3(kBlock), 0,
+                         (hipStream_t)stream, num_rows, emb_dim, row_stride, state_stride, n_uniq, uniq_rows,
+                         seg_offset, sorted_pos, grad, gl, grad_scale, P, M, V, lr_t, eps_t, hyper->beta1,
+                         hyper->beta2, l2);
+    else
+      hipLaunchKernelGGL((adam_rows_all_kernel<VEC, LANES, false>), dim3((unsigned)grid), dim3(kBlock), 0,
+                         (hipStream_t)stream, num_rows, emb_dim, row_stride, state_stride, n_uniq, uniq_rows,
+                         seg_offset, sorted_pos, grad, gl, grad_scale, P, M, V, lr_t, eps_t, hyper->beta1,
+                         hyper->beta2, 0.f);
     return check_launch("rec_adam_rows_all");
   });
+}
+
+extern "C" int rec_adam_rows_all(int64_t num_rows, int32_t emb_dim, int32_t row_stride,
+                                 int32_t state_stride, const int32_t* n_uniq, const int64_t* uniq_rows,
+                                 const int32_t* seg_offset, const int32_t* sorted_pos, const float* grad,
+                                 const rec_grad_layout* grad_layout, const float* grad_scale, float* P,
+                                 float* M, float* V, const rec_adam_hyper* hyper, void* stream) {
+  return adam_rows_all_impl(num_rows, emb_dim, row_stride, state_stride, n_uniq, uniq_rows, seg_offset, sorted_pos,
+                            grad, grad_layout, grad_scale, P, M, V, hyper, 0.f, stream);
+}
+
+extern "C" int rec_adam_rows_all_l2(int64_t num_rows, int32_t emb_dim, int32_t row_stride,
+                                    int32_t state_stride, const int32_t* n_uniq, const int64_t* uniq_rows,
+                                    const int32_t* seg_offset, const int32_t* sorted_pos, const float* grad,
+                                    const rec_grad_layout* grad_layout, const float* grad_scale, float* P,
+                                    float* M, float* V, const rec_adam_hyper* hyper, float l2_coeff, void* stream) {
+  return adam_rows_all_impl(num_rows, emb_dim, row_stride, state_stride, n_uniq, uniq_rows, seg_offset, sorted_pos,
+                            grad, grad_layout, grad_scale, P, M, V, hyper, l2_coeff, stream);
 }

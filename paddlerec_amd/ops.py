@@ -10,7 +10,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import (EPI, AdagradHyper, AdamHyper, CinView, DeepFMDesc, DinDesc, FFMDesc, GemmBImage, GemmDesc, GemmEpilogueArgs, GradLayout,
+from ._lib import (EPI, AdagradHyper, AdamHyper, CinView, DeepFMDesc, DinDesc, FEFMDesc, FFMDesc, GemmBImage, GemmDesc, GemmEpilogueArgs, GradLayout,
                    GradSrc, LazyInit, MultislotDesc, PsAccessor, PsLayout, RecError, check)
 
 _recorder = None        # paddlerec_amd.plan.CallPlan while a step is being recorded
@@ -402,6 +402,112 @@ def ffm_bwd(ids, dense, W, dense_w, dz, dim, ws, out=None, status=None, grad_str
     return row_grad, d_dense_w, d_dense_w_one
 
 
+# ------------------------------------------------------------------ FEFM field-pair bilinear interaction (deepfefm)
+def _fefm_desc(ids, dense, dim, W, what):
+    _chk(ids, torch.int64, "ids")
+    if ids.dim() != 2:
+        raise RecError("%s: ids must be [B, S]" % what)
+    B = ids.shape[0]
+    _chk(dense, torch.float32, "dense")
+    if dense.dim() != 2 or dense.shape[0] != B:
+        raise RecError("%s: dense must be [B, Dn]" % what)
+    width, stride = _chk_table(W, "W")
+    if W.dim() != 2 or width < int(dim):
+        raise RecError("%s: W rows hold %d floats, dim = %d" % (what, width, int(dim)))
+    return B, dense.shape[1], stride
+
+
+def _fefm_ld(t, B, cols, name):
+    if t.dim() != 2 or t.dtype != torch.float32 or not t.is_cuda or t.shape[0] != B or t.shape[1] < cols or \
+            (t.shape[1] > 1 and t.stride(1) != 1):
+        raise RecError("%s must be a float32 device matrix [B, >= %d] with unit column stride" % (name, cols))
+    return t.stride(0) if B > 1 else max(t.stride(0), t.shape[1])
+
+
+def fefm_fwd(ids, dense, W, W1, dense_w_one, FE, dim, ws, status=None, out=None):
+    """ids [B,S] i64, dense [B,Dn] f32, W [N, >= dim] (a padded row stride is fine), W1 [N,1]|[N], dense_w_one [Dn],
+    FE [P,dim,dim] (P = F(F-1)/2 pairs, F = S+Dn) -> y1 [B,1], y2 [B,1], dnn_in [B, S*dim+Dn+P] (or the wider buffer
+    given as out[2]: its row stride is used), ids_all [B,F] i64, status  (rec_fefm_fwd)."""
+    B, Dn, stride = _fefm_desc(ids, dense, dim, W, "fefm_fwd")
+    S, D = ids.shape[1], int(dim)
+    F = S + Dn
+    P = F * (F - 1) // 2
+    N = W.shape[0]
+    _chk(W1, torch.float32, "W1")
+    _chk(dense_w_one, torch.float32, "dense_w_one", (Dn,))
+    _chk(FE, torch.float32, "FE", (P, D, D))
+    if W1.numel() != N:
+        raise RecError("fefm_fwd: W1 must hold one value per row of W")
+    dev = ids.device
+    cols = S * D + Dn + P
+    if out is None:
+        y1 = torch.empty(B, 1, dtype=torch.float32, device=dev)
+        y2 = torch.empty(B, 1, dtype=torch.float32, device=dev)
+        dnn_in = torch.empty(B, cols, dtype=torch.float32, device=dev)
+        ids_all = torch.empty(B, F, dtype=torch.int64, device=dev)
+    else:
+        y1, y2, dnn_in, ids_all = out
+        _chk(y1, torch.float32, "y1")
+        _chk(y2, torch.float32, "y2")
+        _chk(ids_all, torch.int64, "ids_all", (B, F))
+        if y1.numel() != B or y2.numel() != B:
+            raise RecError("fefm_fwd: y1 / y2 must hold B values")
+    ld = _fefm_ld(dnn_in, B, cols, "dnn_in")
+    if status is None:
+        status = new_status(dev)
+    desc = FEFMDesc(B, S, Dn, D, N, stride, 0, ld)
+    nbytes = C.c_size_t(0)
+    check(lib().rec_fefm_fwd_workspace_bytes(C.byref(desc), C.byref(nbytes)), "rec_fefm_fwd_workspace_bytes")
+    w = ws.get(nbytes.value)
+    check(lib().rec_fefm_fwd(C.byref(desc), _p(ids), _p(dense), _p(W), _p(W1), _p(dense_w_one), _p(FE), _p(y1), _p(y2),
+                             _p(dnn_in), _p(ids_all), _p(w), C.c_size_t(w.numel()), _p(status), _stream()),
+          "rec_fefm_fwd")
+    return y1, y2, dnn_in, ids_all, status
+
+
+def fefm_bwd(ids_all, dense, W, FE, dz, d_dnn_in, num_slots, dim, ws, want_d_fe=False, out=None, status=None,
+             grad_stride=None):
+    """ids_all [B,F] i64 (from fefm_fwd), dz [B]|[B,1] = dloss / dlogit, d_dnn_in [B, >= S*dim+Dn+P] = dloss / d dnn_in
+    -> row_grad [B*F, grad_stride] (default: dim rounded up to 4 floats; pad columns and padding positions are 0),
+    d_dense_w_one [Dn], d_FE [P,dim,dim] or None (want_d_fe False: that work is skipped)  (rec_fefm_bwd).  The W1
+    gradient is dz itself, read with grad_div = S over a grouping of the sparse ids [B,S]."""
+    B, Dn, stride = _fefm_desc(ids_all, dense, dim, W, "fefm_bwd")
+    F, D, S = ids_all.shape[1], int(dim), int(num_slots)
+    if S + Dn != F:
+        raise RecError("fefm_bwd: ids_all has %d fields, num_slots + Dn = %d" % (F, S + Dn))
+    P = F * (F - 1) // 2
+    _chk(FE, torch.float32, "FE", (P, D, D))
+    _chk(dz, torch.float32, "dz")
+    if dz.numel() != B:
+        raise RecError("fefm_bwd: dz must hold B values")
+    ld = _fefm_ld(d_dnn_in, B, S * D + Dn + P, "d_dnn_in")
+    gs = int(grad_stride) if grad_stride else (D + 3) // 4 * 4
+    dev = ids_all.device
+    if out is None:
+        row_grad = torch.empty(B * F, gs, dtype=torch.float32, device=dev)
+        d_dense_w_one = torch.empty(Dn, dtype=torch.float32, device=dev)
+        d_FE = torch.empty(P, D, D, dtype=torch.float32, device=dev) if want_d_fe else None
+    else:
+        row_grad, d_dense_w_one, d_FE = out
+        if not want_d_fe:
+            d_FE = None
+    _chk(row_grad, torch.float32, "row_grad", (B * F, gs))
+    _chk(d_dense_w_one, torch.float32, "d_dense_w_one", (Dn,))
+    if want_d_fe:
+        if d_FE is None:
+            raise RecError("fefm_bwd: want_d_fe needs a d_FE tensor in out")
+        _chk(d_FE, torch.float32, "d_FE", (P, D, D))
+    desc = FEFMDesc(B, S, Dn, D, W.shape[0], stride, gs, ld)
+    nbytes = C.c_size_t(0)
+    check(lib().rec_fefm_bwd_workspace_bytes(C.byref(desc), int(bool(want_d_fe)), C.byref(nbytes)),
+          "rec_fefm_bwd_workspace_bytes")
+    w = ws.get(nbytes.value)
+    check(lib().rec_fefm_bwd(C.byref(desc), _p(ids_all), _p(dense), _p(W), _p(FE), _p(dz), _p(d_dnn_in), _p(row_grad),
+                             _p(d_dense_w_one), _p(d_FE), _p(w), C.c_size_t(w.numel()), _p(status), _stream()),
+          "rec_fefm_bwd")
+    return row_grad, d_dense_w_one, d_FE
+
+
 def dense_fold_fwd(S, dense_w, W0, M):
     """M[j,:] = dense_w[j,:] @ W0[(S+j)*D:(S+j+1)*D, :]   (dense embeddings folded into MLP layer 0)."""
     Dn, D = dense_w.shape[-2], dense_w.shape[-1]
@@ -697,9 +803,12 @@ def _hyper(lr, beta1, beta2, eps, step):
 
 
 def sparse_adam_rows(groups, grad, grad_div, P, M, V, step, lr=1e-3, beta1=0.9, beta2=0.999,
-                     eps=1e-8, grad_group=0, grad_group_stride=0, grad_scale=None, partials=None, grad_index=None):
+                     eps=1e-8, grad_group=0, grad_group_stride=0, grad_scale=None, partials=None, grad_index=None,
+                     l2=None):
     """grad_div / grad_group / grad_group_stride: rec_grad_layout (where position pos's row lives in
-    grad); grad_scale: device float[1] clipping coefficient or None."""
+    grad); grad_scale: device float[1] clipping coefficient or None.  l2 given (a float, 0.0 included): L2Decay on the touched
+    rows through rec_sparse_adam_rows_l2, whose zero coefficient runs the kernels of rec_sparse_adam_rows; None: the old
+    entry point."""
     if grad_group <= 0:
         _chk(grad, torch.float32, "grad")
     elif not grad.is_cuda or grad.dtype != torch.float32:
@@ -710,6 +819,13 @@ def sparse_adam_rows(groups, grad, grad_div, P, M, V, step, lr=1e-3, beta1=0.9, 
         if _chk_table(t, n) != (D, sstride) or t.shape[0] != P.shape[0]:
             raise RecError("%s must have the shape of P (M and V share one row stride)" % n)
     h = _hyper(lr, beta1, beta2, eps, step)
+    if l2 is not None:
+        check(lib().rec_sparse_adam_rows_l2(groups.n, D, stride, sstride, _p(groups.n_uniq), _p(groups.uniq_rows),
+                                            _p(groups.seg_offset), _p(groups.sorted_pos), _p(grad),
+                                            C.byref(_gl(grad_div, grad_group, grad_group_stride, partials, grad_index)),
+                                            _p(grad_scale), _p(P), _p(M), _p(V), C.byref(h), float(l2), _stream()),
+              "rec_sparse_adam_rows_l2")
+        return
     check(lib().rec_sparse_adam_rows(groups.n, D, stride, sstride, _p(groups.n_uniq), _p(groups.uniq_rows),
                                      _p(groups.seg_offset), _p(groups.sorted_pos), _p(grad),
                                      C.byref(_gl(grad_div, grad_group, grad_group_stride, partials, grad_index)),
@@ -761,14 +877,23 @@ def adam_record_all(groups, grad, grad1, grad1_div, rec, mv, D, step, lr=1e-3, b
 
 
 def adam_rows_all(groups, grad, grad_div, P, M, V, step, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8,
-                  grad_group=0, grad_group_stride=0, grad_scale=None, partials=None):
-    """lazy_mode=False Adam (dygraph default): every row of P/M/V moves, absent rows with g = 0."""
+                  grad_group=0, grad_group_stride=0, grad_scale=None, partials=None, l2=None):
+    """lazy_mode=False Adam (dygraph default): every row of P/M/V moves, absent rows with g = 0.  l2 given (a float, 0.0
+    included): L2Decay, every row moves with g + l2 * w, through rec_adam_rows_all_l2 (a zero coefficient runs the
+    kernels of rec_adam_rows_all); None: the old entry point."""
     D, stride = _chk_table(P, "P")
     sstride = _chk_table(M, "M")[1]
     for t, n in ((M, "M"), (V, "V")):
         if _chk_table(t, n) != (D, sstride) or t.shape[0] != P.shape[0]:
             raise RecError("%s must have the shape of P (M and V share one row stride)" % n)
     h = _hyper(lr, beta1, beta2, eps, step)
+    if l2 is not None:
+        check(lib().rec_adam_rows_all_l2(P.shape[0], D, stride, sstride, _p(groups.n_uniq), _p(groups.uniq_rows),
+                                         _p(groups.seg_offset), _p(groups.sorted_pos), _p(grad),
+                                         C.byref(_gl(grad_div, grad_group, grad_group_stride, partials)),
+                                         _p(grad_scale), _p(P), _p(M), _p(V), C.byref(h), float(l2), _stream()),
+              "rec_adam_rows_all_l2")
+        return
     check(lib().rec_adam_rows_all(P.shape[0], D, stride, sstride, _p(groups.n_uniq), _p(groups.uniq_rows),
                                   _p(groups.seg_offset), _p(groups.sorted_pos), _p(grad),
                                   C.byref(_gl(grad_div, grad_group, grad_group_stride, partials)),

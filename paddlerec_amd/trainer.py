@@ -10,7 +10,7 @@ What differs by construction: a batch never becomes 28 per-sample NumPy arrays (
 [B,26] / [B,13] device tensors), `loss.backward(); optimizer.step()` is the explicit `train_step` chain of the
 host mirrors, and the AUC buckets stay on the device (read back only when a log line prints them).
 
-    python -m paddlerec_amd.trainer -m <config.yaml> [--model deepfm|fm|ffm|wide_deep|dnn|dcn_v2|din|xdeepfm|dlrm] [-o runner.epochs=1 ...] [--infer]
+    python -m paddlerec_amd.trainer -m <config.yaml> [--model deepfm|fm|ffm|deepfefm|wide_deep|dnn|dcn_v2|din|xdeepfm|dlrm] [-o runner.epochs=1 ...] [--infer]
     python -m torch.distributed.run --nproc-per-node G -m paddlerec_amd.trainer -m <config.yaml>     # collective mode
 """
 import argparse
@@ -24,7 +24,7 @@ from . import checkpoint
 
 logger = logging.getLogger("paddlerec_amd.trainer")
 
-MODELS = ("deepfm", "fm", "ffm", "wide_deep", "dnn", "dcn_v2", "din", "xdeepfm", "dlrm")
+MODELS = ("deepfm", "fm", "ffm", "deepfefm", "wide_deep", "dnn", "dcn_v2", "din", "xdeepfm", "dlrm")
 
 
 # ------------------------------------------------------------------------------------ configuration
@@ -77,6 +77,8 @@ def _dygraph_model(name):
         from .fm import DygraphModel
     elif name == "ffm":
         from .ffm import DygraphModel
+    elif name == "deepfefm":
+        from .deepfefm import DygraphModel
     elif name == "wide_deep":
         from .wide_deep import DygraphModel
     elif name == "dnn":
@@ -208,6 +210,23 @@ def _apply_optimizer_config(config, model, dy_model):
         logger.warning("DEVIATION from the reference's dygraph run: %s updates only the rows a batch touches "
                        "(Adam lazy_mode=True); the reference's dygraph Adam also decays the moments of every "
                        "other row each step", model)
+    if model == "deepfefm":
+        if lazy:
+            logger.warning("DEVIATION from the reference's dygraph run: deepfefm with lazy_mode=True applies Adam and "
+                           "L2Decay(1e-6) only to the table rows a batch touches; the reference's sparse=False Embeddings "
+                           "move every row every step")
+        if getattr(dy_model, "train_field_embeddings", False):
+            logger.warning("DEVIATION from the reference's dygraph run: hyper_parameters.train_field_embeddings=true — the "
+                           "%d field-pair matrices get their gradient, L2Decay(1e-7) and Adam, as in the reference's "
+                           "static-graph model", dy_model.num_pairs)
+        else:
+            logger.info("deepfefm: the %d field-pair matrices stay FROZEN at their initial draw — the reference keeps them "
+                        "in a plain dict (deepfefm/net.py:104), so its dygraph optimizer never sees them; "
+                        "hyper_parameters.train_field_embeddings=true trains them.  They are saved as "
+                        "fefm.field_embeddings (the reference's checkpoints do not hold them)", dy_model.num_pairs)
+        logger.info("deepfefm train mode: Dropout(%.2f) after every element of the DNN's layer list, the last Linear "
+                    "included (deepfefm/net.py:229-234), with the engine's counter-based masks (seed %d)",
+                    getattr(dy_model, "dropout_rate", 0.0), getattr(dy_model, "dropout_seed", 0))
     if model == "dcn_v2":
         logger.info("dcn_v2 train mode: Dropout(%.2f) after every element of the DNN tower (dcn_v2/net.py:181-183) with the "
                     "engine's counter-based masks (seed %d; Paddle's own mask stream is not reproducible), L2Decay(%g) on "
