@@ -871,7 +871,16 @@ int rec_crossnet_v2_layer_fwd(const rec_crossnet_v2_desc* desc, const float* X0,
                               const float* bias, float* Xnext, float* U_saved, void* workspace,
                               size_t workspace_bytes, void* stream);
 /* Given dXnext = d x_{l+1}:  dW [d,d], db [d], dXl = d x_l (may alias dXnext);  dX0_acc (+)= dXnext * U_l
- * (accumulate_dx0 = 0: overwritten);  fold_dx0 != 0: dXl also receives dX0_acc (the first layer, x_l = x_0). */
+ * (accumulate_dx0 = 0: overwritten, never read);  fold_dx0 != 0: dXl also receives dX0_acc (the first layer, x_l = x_0).
+ * GRADIENT STRIDES (ld_dxnext, ld_acc, ld_dxl; 0 = d) are call arguments, not descriptor fields, so the workspace query
+ * cannot see them, and the split-K partials of the GEMM that writes dXl are [splits][B][ld_dxl].  The contract, for this
+ * entry point and for rec_crossnet_mix_layer_bwd:
+ *   - the backward reads desc->ld_out for nothing but sizing: a caller whose gradient buffers are strided wider than the
+ *     strides of its descriptor sets ld_out to the widest of them in the descriptor it hands to the query AND to the call,
+ *     and bwd_bytes then covers the call;
+ *   - every argument and workspace check of the call (strides < d: REC_EINVAL; workspace smaller than what the GEMMs
+ *     need AT THE STRIDES PASSED: REC_EWORKSPACE) is made before the first launch: a negative status means that no
+ *     output and no byte of dX0_acc was written.  A call either returns 0 with every output complete, or did nothing. */
 int rec_crossnet_v2_layer_bwd(const rec_crossnet_v2_desc* desc, const float* X0, const float* Xl, const float* W,
                               const float* U_saved, const float* dXnext, int32_t ld_dxnext, float* dX0_acc,
                               int32_t ld_acc, int32_t accumulate_dx0, int32_t fold_dx0, float* dXl,
@@ -892,7 +901,7 @@ int rec_crossnet_mix_layer_fwd(const rec_crossnet_mix_desc* desc, const float* X
                                void* workspace, size_t workspace_bytes, void* stream);
 /* gU, gV [E,d,r], gC [E,r,r], gbias [d] are written; the gating layers are shared by all cross layers
  * (net.py:267-268): g_gate_w [d,E] / g_gate_b [E] are overwritten when accumulate_gate == 0, added to otherwise.
- * dXl must not alias dXnext.  dX0_acc / fold_dx0 as above. */
+ * dXl must not alias dXnext (REC_EINVAL).  dX0_acc / fold_dx0 / gradient strides and the all-or-nothing contract as above. */
 int rec_crossnet_mix_layer_bwd(const rec_crossnet_mix_desc* desc, const float* X0, const float* Xl, const float* U,
                                const float* V, const float* C, const float* bias, const float* gate_w,
                                const float* t1, const float* t2, const float* prob, const float* dXnext,

@@ -64,6 +64,8 @@ using namespace rec;
 static int v2_check(const rec_crossnet_v2_desc* d) {
   REC_REQUIRE(d, REC_EINVAL, "desc is NULL");
   REC_REQUIRE(d->batch >= 0 && d->d > 0, REC_EINVAL, "bad sizes B=%lld d=%d", (long long)d->batch, d->d);
+  for (int v : {d->ld_x0, d->ld_xl, d->ld_out, d->ld_u})
+    REC_REQUIRE(v == 0 || v >= d->d, REC_EINVAL, "row stride %d < d %d", v, d->d);
   return REC_OK;
 }
 static int ldx(int ld, int d) { return ld > 0 ? ld : d; }
@@ -82,8 +84,9 @@ extern "C" int rec_crossnet_v2_layer_workspace_bytes(const rec_crossnet_v2_desc*
                                                      size_t* bwd_bytes) {
   REC_TRY(v2_check(d));
   const int n = d->d;
-  // split-K partials are [splits][M][ldc]: sized for the widest row stride the descriptor names (gradient buffers
-  // handed to the backward must not be strided wider than that)
+  // split-K partials are [splits][M][ldc]: sized for the widest row stride the descriptor names.  The gradient buffers
+  // of the backward are call arguments: a caller whose buffers are wider names their widest stride in ld_out (which the
+  // backward does not otherwise read); the backward itself re-checks at the strides it was handed before it launches
   const int lw = v2_ldmax(d);
   if (fwd_bytes) *fwd_bytes = gemm_ws(gd(d->batch, n, n, lw, n, lw, 0, 0, REC_EPI_CROSS));
   if (bwd_bytes) {
@@ -123,26 +126,35 @@ extern "C" int rec_crossnet_v2_layer_bwd(const rec_crossnet_v2_desc* d, const fl
   REC_REQUIRE(X0 && Xl && W && U_saved && dXnext && dX0_acc && dXl && dW && db, REC_EINVAL,
               "null pointer argument");
   const int n = d->d;
+  const int ldn = ldx(ld_dxnext, n), lacc = ldx(ld_acc, n), ldl = ldx(ld_dxl, n);
+  REC_REQUIRE(ldn >= n && lacc >= n && ldl >= n, REC_EINVAL, "gradient row stride < d %d (%d, %d, %d)", n, ldn, lacc, ldl);
+  const rec_gemm_desc g_dw = gd(n, n, (int)d->batch, ldx(d->ld_xl, n), n, n, 1, 0, REC_EPI_NONE);
+  const rec_gemm_desc g_dx = gd(d->batch, n, n, n, n, ldl, 0, 1, REC_EPI_ADD);
+  // ALL of the call's workspace needs are settled here, before the first launch: the query sized the split-K partials
+  // for the strides of the descriptor, the two GEMMs below run at the strides of THIS call (ld_dxl is an argument)
   size_t need = 0;
   rec_crossnet_v2_layer_workspace_bytes(d, nullptr, &need);
-  REC_REQUIRE(workspace && workspace_bytes >= need, REC_EWORKSPACE, "workspace %zu < %zu", workspace_bytes, need);
+  need = max2(need, align_up((size_t)d->batch * n * sizeof(float), 256) + max2(gemm_ws(g_dw), gemm_ws(g_dx)));
+  REC_REQUIRE(workspace && workspace_bytes >= need, REC_EWORKSPACE,
+              "workspace %zu < %zu (gradient buffers wider than the descriptor's strides: name the widest in ld_out)",
+              workspace_bytes, need);
   Carve c(workspace);
   float* dU = c.take((size_t)d->batch * n);
   void* gws = (char*)workspace + c.off;
   const size_t gws_bytes = workspace_bytes - c.off;
-  REC_TRY(rec_cross_bwd_prep(d->batch, n, dXnext, ldx(ld_dxnext, n), X0, ldx(d->ld_x0, n), U_saved,
-                             ldx(d->ld_u, n), dU, n, dX0_acc, ldx(ld_acc, n), accumulate_dx0, stream));
+  REC_TRY(rec_cross_bwd_prep(d->batch, n, dXnext, ldn, X0, ldx(d->ld_x0, n), U_saved, ldx(d->ld_u, n), dU, n, dX0_acc,
+                             lacc, accumulate_dx0, stream));
   {   // dW = X_l^T dU, db = colsum(dU)
-    const rec_gemm_desc g = gd(n, n, (int)d->batch, ldx(d->ld_xl, n), n, n, 1, 0, REC_EPI_NONE);
+    const rec_gemm_desc& g = g_dw;
     rec_gemm_epilogue_args a = {};
     a.b_colsum = db;
     REC_TRY(rec_gemm_f32(&g, Xl, dU, dW, &a, gws, gws_bytes, stream));
   }
   {   // d X_l = d X_{l+1} + dU W^T (+ dX0_acc)
-    const rec_gemm_desc g = gd(d->batch, n, n, n, n, ldx(ld_dxl, n), 0, 1, REC_EPI_ADD);
+    const rec_gemm_desc& g = g_dx;
     rec_gemm_epilogue_args a = {};
-    a.aux1 = dXnext; a.ld_aux1 = ldx(ld_dxnext, n);
-    if (fold_dx0) { a.aux0 = dX0_acc; a.ld_aux0 = ldx(ld_acc, n); }
+    a.aux1 = dXnext; a.ld_aux1 = ldn;
+    if (fold_dx0) { a.aux0 = dX0_acc; a.ld_aux0 = lacc; }
     REC_TRY(rec_gemm_f32(&g, dU, W, dXl, &a, gws, gws_bytes, stream));
   }
   return REC_OK;
@@ -153,6 +165,8 @@ static int mix_check(const rec_crossnet_mix_desc* d) {
   REC_REQUIRE(d, REC_EINVAL, "desc is NULL");
   REC_REQUIRE(d->batch >= 0 && d->d > 0 && d->rank > 0 && d->experts > 0 && d->experts <= 64, REC_EINVAL,
               "bad sizes B=%lld d=%d r=%d E=%d", (long long)d->batch, d->d, d->rank, d->experts);
+  for (int v : {d->ld_x0, d->ld_xl, d->ld_out})
+    REC_REQUIRE(v == 0 || v >= d->d, REC_EINVAL, "row stride %d < d %d", v, d->d);
   return REC_OK;
 }
 
@@ -262,10 +276,18 @@ extern "C" int rec_crossnet_mix_layer_bwd(const rec_crossnet_mix_desc* d, const 
   const int64_t B = d->batch;
   const int lx0 = ldx(d->ld_x0, n), lxl = ldx(d->ld_xl, n), ldn = ldx(ld_dxnext, n), lacc = ldx(ld_acc, n),
             ldl = ldx(ld_dxl, n);
+  REC_REQUIRE(ldn >= n && lacc >= n && ldl >= n, REC_EINVAL, "gradient row stride < d %d (%d, %d, %d)", n, ldn, lacc, ldl);
   hipStream_t st = (hipStream_t)stream;
+  // ALL of the call's workspace needs are settled here, before the first launch (as rec_crossnet_v2_layer_bwd): the two
+  // GEMMs that write dXl run at ld_dxl, an argument the query never saw
+  const rec_gemm_desc g_dxv = gd(B, n, r, r, r, ldl, 0, 1, REC_EPI_ADD);
+  const rec_gemm_desc g_dxg = gd(B, n, E, E, E, ldl, 0, 1, REC_EPI_ADD);
   size_t need = 0;
   rec_crossnet_mix_layer_workspace_bytes(d, nullptr, &need);
-  REC_REQUIRE(workspace && workspace_bytes >= need, REC_EWORKSPACE, "workspace %zu < %zu", workspace_bytes, need);
+  need = max2(need, need - mix_gemm_ws(d) + max2(gemm_ws(g_dxv), gemm_ws(g_dxg)));
+  REC_REQUIRE(workspace && workspace_bytes >= need, REC_EWORKSPACE,
+              "workspace %zu < %zu (gradient buffers wider than the descriptor's strides: name the widest in ld_out)",
+              workspace_bytes, need);
   Carve c(workspace);
   float* u = c.take((size_t)B * n);
   float* du = c.take((size_t)B * n);
@@ -322,7 +344,7 @@ extern "C" int rec_crossnet_mix_layer_bwd(const rec_crossnet_mix_desc* d, const 
       REC_TRY(rec_gemm_f32(&g, Xl, da, gV + (size_t)e * n * r, &a, gws, gwb, stream));
     }
     {   // d x_l (+)= da V_e^T   (starts from d x_{l+1}: the residual path)
-      const rec_gemm_desc g = gd(B, n, r, r, r, ldl, 0, 1, REC_EPI_ADD);
+      const rec_gemm_desc& g = g_dxv;
       a = {};
       a.aux1 = e == 0 ? dXnext : dXl; a.ld_aux1 = e == 0 ? ldn : ldl;
       REC_TRY(rec_gemm_f32(&g, da, Ve, dXl, &a, gws, gwb, stream));
@@ -336,7 +358,7 @@ extern "C" int rec_crossnet_mix_layer_bwd(const rec_crossnet_mix_desc* d, const 
     add_into((int64_t)n * E, g_gate_w, gw, accumulate_gate, st);
     REC_TRY(rec_colsum(B, E, E, dgate, gb, gws, gwb, stream));
     add_into(E, g_gate_b, gb, accumulate_gate, st);
-    const rec_gemm_desc g2 = gd(B, n, E, E, E, ldl, 0, 1, REC_EPI_ADD);
+    const rec_gemm_desc& g2 = g_dxg;
     a = {};
     a.aux1 = dXl; a.ld_aux1 = ldl;
     if (fold_dx0) { a.aux0 = dX0_acc; a.ld_aux0 = lacc; }

@@ -1524,7 +1524,10 @@ def crossnet_v2_layer_bwd(x0, xl, W, u, dxnext, dx0_acc, accumulate_dx0, fold_dx
     B, d = xl.shape
     if out is None:
         out = torch.empty(B, d, dtype=torch.float32, device=xl.device)
-    desc = _lib.CrossV2Desc(B, d, _ld(x0, "x0"), _ld(xl, "xl"), d, _ld(u, "u"))
+    # ld_out: the widest gradient row stride of this call, so that the workspace query covers the split-K partials of
+    # the GEMM that writes `out` (include/recengine.h: the backward reads ld_out for nothing else)
+    desc = _lib.CrossV2Desc(B, d, _ld(x0, "x0"), _ld(xl, "xl"),
+                            max(d, _ld(dxnext, "dxnext"), _ld(dx0_acc, "dx0_acc"), _ld(out, "out")), _ld(u, "u"))
     nb = C.c_size_t(0)
     check(lib().rec_crossnet_v2_layer_workspace_bytes(C.byref(desc), None, C.byref(nb)))
     w = ws.get(nb.value)
@@ -1563,7 +1566,8 @@ def crossnet_mix_layer_bwd(x0, xl, U, V, Cm, bias, gate_w, t1, t2, prob, dxnext,
     E, _, r = U.shape
     if out is None:
         out = torch.empty(B, d, dtype=torch.float32, device=xl.device)
-    desc = _lib.CrossMixDesc(B, d, r, E, _ld(x0, "x0"), _ld(xl, "xl"), d)
+    desc = _lib.CrossMixDesc(B, d, r, E, _ld(x0, "x0"), _ld(xl, "xl"),          # ld_out: as crossnet_v2_layer_bwd
+                             max(d, _ld(dxnext, "dxnext"), _ld(dx0_acc, "dx0_acc"), _ld(out, "out")))
     nb = C.c_size_t(0)
     check(lib().rec_crossnet_mix_layer_workspace_bytes(C.byref(desc), None, C.byref(nb)))
     w = ws.get(nb.value)

@@ -101,3 +101,95 @@ def test_more_argument_validation_without_gpu(engine_lib):
     nl = C.c_int64(0)
     assert L.rec_count_lines(None, 10, 1, C.byref(nl)) == -1
     assert L.rec_count_lines(b"a\nb\nc", 5, 4, C.byref(nl)) == 0 and nl.value == 3
+
+
+def test_cross_entry_points_reject_bad_arguments_without_gpu(engine_lib):
+    """Host checks of the CrossNet glue kernels and layer entry points: they return before any launch, so they can be
+    called on a GPU-less host with dummy non-null pointer values (tests/test_cross_layers_gpu.py runs the kernels)."""
+    import ctypes as C
+    from paddlerec_amd import _lib
+    L = engine_lib
+    p = C.c_void_p(4096)                                     # never dereferenced: every call below is refused first
+    # softmax over the experts: 1 <= E <= 64, leading dimensions >= E
+    assert L.rec_softmax_rows(4, 65, p, 65, p, 65, None) == -1
+    assert L.rec_softmax_rows(4, 0, p, 4, p, 4, None) == -1
+    assert L.rec_softmax_rows(4, 5, p, 4, p, 5, None) == -1
+    assert L.rec_softmax_rows(4, 5, p, 5, p, 4, None) == -1
+    assert L.rec_softmax_rows_bwd(4, 65, p, 65, p, 65, p, 65, None) == -1
+    for bad in range(3):
+        lds = [5, 5, 5]
+        lds[bad] = 4
+        assert L.rec_softmax_rows_bwd(4, 5, p, lds[0], p, lds[1], p, lds[2], None) == -1
+    # the streaming glue: every leading dimension >= n
+    for bad in range(5):
+        lds = [8] * 5
+        lds[bad] = 7
+        assert L.rec_cross_bwd_prep(3, 8, p, lds[0], p, lds[1], p, lds[2], p, lds[3], p, lds[4], 0, None) == -1
+        assert L.rec_moe_bwd_prep(3, 8, p, lds[0], p, lds[1], p, lds[2], p, 1, p, lds[3], p, lds[4], 0, p, 1, None) == -1
+    assert L.rec_moe_bwd_prep(3, 8, p, 8, p, 8, p, 8, p, 0, p, 8, p, 8, 0, p, 1, None) == -1      # prob_stride < 1
+    assert L.rec_cross_bwd_prep(0, 8, None, 8, None, 8, None, 8, None, 8, None, 8, 0, None) == 0  # m = 0: nothing to do
+    # global-norm clip
+    assert L.rec_clip_scale(p, 0.0, p, None) == -1
+    assert L.rec_clip_scale(p, -1.0, p, None) == -1
+    assert L.rec_clip_scale(None, 1.0, p, None) == -1
+    # CrossNetMix: experts <= 64, rank > 0, dXl must not alias dXnext (batch > 0: batch == 0 returns success first)
+    n = C.c_size_t(0)
+    assert L.rec_crossnet_mix_layer_workspace_bytes(C.byref(_lib.CrossMixDesc(8, 12, 4, 65, 0, 0, 0)), C.byref(n), None) == -1
+    assert L.rec_crossnet_mix_layer_workspace_bytes(C.byref(_lib.CrossMixDesc(8, 12, 0, 4, 0, 0, 0)), C.byref(n), None) == -1
+    ok = _lib.CrossMixDesc(8, 12, 4, 3, 0, 0, 0)
+
+    def mix_bwd(desc, dxnext, dxl, ld_dxnext=0, ld_acc=0, ld_dxl=0):
+        return L.rec_crossnet_mix_layer_bwd(C.byref(desc), *[p] * 10, dxnext, ld_dxnext, p, ld_acc, 0, 0, dxl, ld_dxl,
+                                            *[p] * 6, 0, p, C.c_size_t(1 << 30), None)
+    q = C.c_void_p(8192)
+    assert mix_bwd(ok, p, p) == -1 and b"alias" in L.rec_last_error()
+    assert mix_bwd(_lib.CrossMixDesc(8, 12, 4, 65, 0, 0, 0), p, q) == -1
+    assert mix_bwd(_lib.CrossMixDesc(8, 12, 0, 3, 0, 0, 0), p, q) == -1
+    assert mix_bwd(_lib.CrossMixDesc(0, 12, 4, 3, 0, 0, 0), p, p) == 0
+    # row strides below d — descriptor fields and the gradient strides of the call — are refused before anything runs
+    assert mix_bwd(_lib.CrossMixDesc(8, 12, 4, 3, 11, 0, 0), p, q) == -1
+    for k in range(3):
+        lds = [0, 0, 0]
+        lds[k] = 11
+        assert mix_bwd(ok, p, q, *lds) == -1 and b"stride" in L.rec_last_error()
+
+    def v2_bwd(desc, ld_dxnext=0, ld_acc=0, ld_dxl=0, ws_bytes=1 << 30):
+        return L.rec_crossnet_v2_layer_bwd(C.byref(desc), p, p, p, p, p, ld_dxnext, p, ld_acc, 0, 0, q, ld_dxl, p, p, p,
+                                           C.c_size_t(ws_bytes), None)
+    assert v2_bwd(_lib.CrossV2Desc(8, 12, 0, 11, 0, 0)) == -1
+    for k in range(3):
+        lds = [0, 0, 0]
+        lds[k] = 11
+        assert v2_bwd(_lib.CrossV2Desc(8, 12, 0, 0, 0, 0), *lds) == -1 and b"stride" in L.rec_last_error()
+    assert v2_bwd(_lib.CrossV2Desc(0, 12, 0, 0, 0, 0)) == 0
+
+
+def test_cross_layer_workspace_covers_the_strides_of_the_call(engine_lib):
+    """include/recengine.h, gradient strides: at B 64, d 156 the dXl GEMM splits K and its partials are
+    [splits][B][ld_dxl].  A dXl of row stride 176 needs more than the bwd_bytes of a descriptor that names no stride
+    above 156: the call is refused with REC_EWORKSPACE BEFORE its first launch (host arithmetic only — this runs without
+    a GPU), and a descriptor whose ld_out names 176 reports a bwd_bytes that covers it."""
+    import ctypes as C
+    from paddlerec_amd import _lib
+    L = engine_lib
+    B, d, wide = 64, 156, 176
+    sp = C.c_int32(0)
+    assert L.rec_gemm_plan_splits(C.byref(_lib.GemmDesc(B, d, d, d, d, wide, 0, 1, 7, 0)), 0, C.byref(sp)) == 0
+    need_gemm = {}
+    for ldc in (d, wide):
+        n = C.c_size_t(0)
+        assert L.rec_gemm_f32_workspace_bytes(C.byref(_lib.GemmDesc(B, d, d, d, d, ldc, 0, 1, 7, 0)), C.byref(n)) == 0
+        need_gemm[ldc] = n.value
+    plain, named = C.c_size_t(0), C.c_size_t(0)
+    assert L.rec_crossnet_v2_layer_workspace_bytes(C.byref(_lib.CrossV2Desc(B, d, 0, 0, 0, 0)), None, C.byref(plain)) == 0
+    assert L.rec_crossnet_v2_layer_workspace_bytes(C.byref(_lib.CrossV2Desc(B, d, 0, 0, wide, 0)), None,
+                                                   C.byref(named)) == 0
+    du = (B * d * 4 + 255) // 256 * 256
+    assert named.value >= du + need_gemm[wide] and named.value >= plain.value
+    if sp.value > 1:
+        assert need_gemm[wide] > need_gemm[d]
+    p, q = C.c_void_p(4096), C.c_void_p(8192)
+    if du + need_gemm[wide] > plain.value:
+        rc = L.rec_crossnet_v2_layer_bwd(C.byref(_lib.CrossV2Desc(B, d, 0, 0, 0, 0)), p, p, p, p, p, 0, p, 0, 0, 1, q, wide,
+                                         p, p, p, C.c_size_t(plain.value), None)
+        assert rc == -3 and b"ld_out" in L.rec_last_error()

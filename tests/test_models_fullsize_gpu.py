@@ -43,6 +43,19 @@ def test_dcn_v2_crossnet_full_size_properties(engine_lib):
     sc = m2._scalar("scale")
     assert 0.0 < float(sc.item()) <= 1.0
     np.testing.assert_allclose(float(sc.item()), 10.0 / max(float(ss.item()) ** 0.5, 10.0), rtol=1e-6)
+    # ... and the engine's sumsq itself against float64 torch on the gradients of that last step (rec_sumsq over the flat
+    # dense gradients + rec_sparse_rows_sumsq over the MERGED rows; a wrong sum would pass the line above).  Lookups of
+    # the padding id 0 contribute nothing to the sparse part.
+    dense_ss = float(m2.dense.grad.double().pow(2).sum().item())
+    rows = ids.reshape(-1)
+    keep = rows != 0
+    uniq, inv = torch.unique(rows[keep], return_inverse=True)
+    merged = torch.zeros(uniq.numel(), 40, dtype=torch.float64, device=DEV)
+    merged.index_add_(0, inv, m2._last_dfeat[:, :26 * 40].reshape(-1, 40)[keep].double())
+    sparse_ss = float(merged.pow(2).sum().item())
+    assert dense_ss > 0.0 and sparse_ss > 0.0
+    assert float(ss.item()) >= dense_ss
+    np.testing.assert_allclose(float(ss.item()), dense_ss + sparse_ss, rtol=1e-5)
 
 
 def test_din_attention_full_size_properties(engine_lib):
