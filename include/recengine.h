@@ -1354,6 +1354,49 @@ int rec_fefm_bwd(const rec_fefm_desc* desc, const int64_t* ids_all, const float*
                  const float* dz, const float* d_dnn_in, float* row_grad, float* d_dense_w_one, float* d_FE,
                  void* workspace, size_t workspace_bytes, int32_t* status, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * DCN: the vector-form cross network of Deep & Cross, models/rank/dcn/net.py:117-135 (_cross_layer, _cross_net).
+ * ONE weight w [d] and ONE bias b [d] are shared by all L layers:
+ *   s_l[r]    = <x_l[r,:], w>                                   one scalar per sample row and layer
+ *   x_{l+1}   = x_0 * s_l + b + x_l                             x_0 = the feature row, d floats (247)
+ *   l2        = l2_coeff * sum_l sum_{r,k} (x_l[r,k] * w[k])^2  a sum over the batch, not a mean
+ * The whole stack runs in one pass over a row: one 64-lane wave per row keeps x_0, x_l, w and b in registers.
+ * Built for 1 <= d <= 512 (any d, multiple of 4 or not) and 1 <= num_layers <= 64; anything else, or a row stride
+ * below d, is REC_EINVAL before any launch.  batch == 0 is a no-op: nothing is launched and no output is written.  Rows whose base address and stride are
+ * multiples of 16 bytes move as 16-byte vectors; columns at or beyond d are never read or written.  Exact f32.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+  int64_t batch;          /* B */
+  int32_t d;              /* floats per row (S*D + Dn = 247) */
+  int32_t num_layers;     /* L (cross_num: 2) */
+  int64_t ld_x0;          /* floats between consecutive rows of X0 (>= d) */
+  int64_t ld_out;         /* ... of the forward's XL (>= d): XL may be a column block of a wider buffer */
+  int64_t ld_dxl;         /* ... of the backward's dXL (>= d; ignored by the rank-1 form) */
+  int64_t ld_dx0;         /* ... of the backward's dX0 (>= d) */
+  float l2_coeff;         /* coefficient of the l2 term in the loss (the reference: 1); 0 skips its arithmetic */
+  int32_t accumulate_dx0; /* backward: 0 = dX0 is written, 1 = dX0 += (the DNN's layer-0 dX is already there) */
+} rec_dcn_cross_desc;
+
+/* Bytes of `workspace` for one shape: the backward's per-block partials of d_w / d_b; the forward's per-block l2
+ * partials fit in the same figure. */
+int rec_dcn_cross_bwd_workspace_bytes(const rec_dcn_cross_desc* desc, size_t* bytes);
+/* X0 [B,ld_x0]; w, b [d] -> XL [B,ld_out] = x_L;  saved [B,L] = s_l[r] at r*L + l, or NULL;  l2_out [1] or NULL.
+ * Inference passes saved = l2_out = NULL: nothing is stored or summed for them and no workspace is needed.  With l2_out
+ * the workspace is required; the per-block partials are folded in block order (two runs are bit-identical). */
+int rec_dcn_cross_fwd(const rec_dcn_cross_desc* desc, const float* X0, const float* w, const float* b, float* XL,
+                      float* saved, float* l2_out, void* workspace, size_t workspace_bytes, void* stream);
+/* Backward of the stack AND of its l2 term (coefficient l2_coeff) for dXL [B,ld_dxl] = dloss / d x_L.  x_1 .. x_{L-1} are
+ * rebuilt in registers from X0 and `saved` (x_l = x_0 * (1 + s_0 + .. + s_{l-1}) + l * b).  With g_L = dXL and, for
+ * l = L-1 .. 0,  t_l = <g_{l+1}, x_0>,  g_l = g_{l+1} + t_l * w + 2 * l2_coeff * x_l * w^2:
+ *   dX0 [B,ld_dx0] (+)= g_0 + sum_l g_{l+1} * s_l                     (desc->accumulate_dx0)
+ *   d_w [d] = sum_r sum_l (t_l * x_l + 2 * l2_coeff * x_l^2 * w),    d_b [d] = sum_r sum_l g_{l+1}
+ * d_w / d_b are per-block partials over a fixed row range, folded in block order (two runs are bit-identical).
+ * Rank-1 form: dXL == NULL with dz [B] and u [d] non-NULL reads the upstream gradient as dz[r] * u[k] (the one-logit
+ * head behind the stack: u = the tail of fc.weight) — no [B,d] matrix is made or read.  Otherwise dz / u are ignored. */
+int rec_dcn_cross_bwd(const rec_dcn_cross_desc* desc, const float* X0, const float* w, const float* b,
+                      const float* saved, const float* dXL, const float* dz, const float* u, float* dX0, float* d_w,
+                      float* d_b, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,6 +35,13 @@ class FEFMDesc(C.Structure):
                 ("num_rows", C.c_int64), ("row_stride", C.c_int32), ("grad_stride", C.c_int32), ("ld", C.c_int64)]
 
 
+class DcnCrossDesc(C.Structure):
+    """rec_dcn_cross_desc (include/recengine.h)."""
+    _fields_ = [("batch", C.c_int64), ("d", C.c_int32), ("num_layers", C.c_int32), ("ld_x0", C.c_int64),
+                ("ld_out", C.c_int64), ("ld_dxl", C.c_int64), ("ld_dx0", C.c_int64), ("l2_coeff", C.c_float),
+                ("accumulate_dx0", C.c_int32)]
+
+
 class DeepFMNet(C.Structure):
     """rec_deepfm_net (include/recengine.h): the model of rec_deepfm_train_step as pointers into caller-owned memory."""
     MAX_LINEAR = 8
@@ -196,6 +203,9 @@ SIGNATURES = {
     "rec_fefm_fwd": (C.c_int, [C.POINTER(FEFMDesc)] + [_P] * 11 + [_SZ, _P, _P]),
     "rec_fefm_bwd_workspace_bytes": (C.c_int, [C.POINTER(FEFMDesc), _I32, C.POINTER(_SZ)]),
     "rec_fefm_bwd": (C.c_int, [C.POINTER(FEFMDesc)] + [_P] * 10 + [_SZ, _P, _P]),
+    "rec_dcn_cross_bwd_workspace_bytes": (C.c_int, [C.POINTER(DcnCrossDesc), C.POINTER(_SZ)]),
+    "rec_dcn_cross_fwd": (C.c_int, [C.POINTER(DcnCrossDesc)] + [_P] * 7 + [_SZ, _P]),
+    "rec_dcn_cross_bwd": (C.c_int, [C.POINTER(DcnCrossDesc)] + [_P] * 11 + [_SZ, _P]),
     "rec_dense_fold_fwd": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P]),
     "rec_dense_fold_bwd": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _I32, _P]),
     "rec_dense_fold_fwd_full": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P]),

@@ -10,7 +10,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import (EPI, AdagradHyper, AdamHyper, CinView, DeepFMDesc, DinDesc, FEFMDesc, FFMDesc, GemmBImage, GemmDesc, GemmEpilogueArgs, GradLayout,
+from ._lib import (EPI, AdagradHyper, AdamHyper, CinView, DcnCrossDesc, DeepFMDesc, DinDesc, FEFMDesc, FFMDesc, GemmBImage, GemmDesc, GemmEpilogueArgs, GradLayout,
                    GradSrc, LazyInit, MultislotDesc, PsAccessor, PsLayout, RecError, check)
 
 _recorder = None        # paddlerec_amd.plan.CallPlan while a step is being recorded
@@ -506,6 +506,116 @@ def fefm_bwd(ids_all, dense, W, FE, dz, d_dnn_in, num_slots, dim, ws, want_d_fe=
                              _p(d_dense_w_one), _p(d_FE), _p(w), C.c_size_t(w.numel()), _p(status), _stream()),
           "rec_fefm_bwd")
     return row_grad, d_dense_w_one, d_FE
+
+
+# ------------------------------------------------------------------ DCN vector-form cross network (rank/dcn)
+def _dcn_rows(t, B, d, name):
+    """A [B, d] float32 device matrix with unit column stride (a column block of a wider buffer is fine) -> row stride."""
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or \
+            tuple(t.shape) != (B, d) or (d > 1 and t.stride(1) != 1):
+        raise RecError("%s must be a float32 device matrix [%d, %d] with unit column stride" % (name, B, d))
+    ld = t.stride(0) if B > 1 else max(t.stride(0), d)
+    if ld < d:
+        raise RecError("%s: row stride %d < d %d" % (name, ld, d))
+    return ld
+
+
+def _dcn_vec(t, d, name):
+    _chk(t, torch.float32, name)
+    if t.numel() != d:
+        raise RecError("%s must hold d = %d floats" % (name, d))
+
+
+def dcn_cross_fwd(x0, w, b, num_layers, ws, l2_coeff=1.0, want_saved=True, want_l2=True, out=None):
+    """The whole cross stack of dcn/net.py:117-135 in one pass (rec_dcn_cross_fwd): x0 [B,d] (rows may be strided), w / b
+    [d] shared by the num_layers layers -> (x_L [B,d], saved [B,L] = the per-row scalars s_l = <x_l, w> or None,
+    l2 [1] = l2_coeff * sum_l sum (x_l * w)^2 or None).  want_saved / want_l2 False: the inference form, nothing is
+    stored or summed for them.  out = (x_L, saved, l2): x_L may be a column block of a wider buffer."""
+    if x0.dim() != 2:
+        raise RecError("dcn_cross_fwd: x0 must be [B, d]")
+    B, d = x0.shape
+    L = int(num_layers)
+    ld_x0 = _dcn_rows(x0, B, d, "x0")
+    _dcn_vec(w, d, "w")
+    _dcn_vec(b, d, "b")
+    dev = x0.device
+    xl, saved, l2 = out if out is not None else (None, None, None)
+    if xl is None:
+        xl = torch.empty(B, d, dtype=torch.float32, device=dev)
+    ld_out = _dcn_rows(xl, B, d, "x_L")
+    if want_saved:
+        if saved is None:
+            saved = torch.empty(B, max(L, 0), dtype=torch.float32, device=dev)
+        _chk(saved, torch.float32, "saved", (B, L))
+    else:
+        saved = None
+    if want_l2:
+        if l2 is None:
+            l2 = torch.empty(1, dtype=torch.float32, device=dev)
+        _chk(l2, torch.float32, "l2", (1,))
+        if B == 0:
+            l2.zero_()
+    else:
+        l2 = None
+    desc = DcnCrossDesc(B, d, L, ld_x0, ld_out, 0, 0, float(l2_coeff), 0)
+    wk = None
+    if want_l2:
+        nbytes = C.c_size_t(0)
+        check(lib().rec_dcn_cross_bwd_workspace_bytes(C.byref(desc), C.byref(nbytes)), "rec_dcn_cross_bwd_workspace_bytes")
+        wk = ws.get(nbytes.value)
+    check(lib().rec_dcn_cross_fwd(C.byref(desc), _p(x0), _p(w), _p(b), _p(xl), _p(saved), _p(l2), _p(wk),
+                                  C.c_size_t(wk.numel() if wk is not None else 0), _stream()), "rec_dcn_cross_fwd")
+    return xl, saved, l2
+
+
+def dcn_cross_bwd(x0, w, b, saved, dxl, ws, l2_coeff=1.0, accumulate=False, out=None, dz=None, u=None):
+    """Backward of dcn_cross_fwd and of its l2 term (rec_dcn_cross_bwd): dxl [B,d] = dloss / d x_L (rows may be strided)
+    -> (dx0 [B,d], d_w [d], d_b [d]).  out = (dx0, d_w, d_b); accumulate=True adds into out[0] (required then) instead
+    of writing it.  Rank-1 form: dxl=None with dz [B]|[B,1] and u [d] reads the upstream gradient as dz[r] * u[k]."""
+    if x0.dim() != 2:
+        raise RecError("dcn_cross_bwd: x0 must be [B, d]")
+    B, d = x0.shape
+    ld_x0 = _dcn_rows(x0, B, d, "x0")
+    _dcn_vec(w, d, "w")
+    _dcn_vec(b, d, "b")
+    _chk(saved, torch.float32, "saved")
+    if saved.dim() != 2 or saved.shape[0] != B:
+        raise RecError("dcn_cross_bwd: saved must be [B, L]")
+    L = saved.shape[1]
+    ld_dxl = 0
+    if dxl is not None:
+        ld_dxl = _dcn_rows(dxl, B, d, "dxl")
+        dz = u = None
+    else:
+        if dz is None or u is None:
+            raise RecError("dcn_cross_bwd: give dxl, or dz and u (the rank-1 form)")
+        _chk(dz, torch.float32, "dz")
+        if dz.numel() != B:
+            raise RecError("dcn_cross_bwd: dz must hold B values")
+        _dcn_vec(u, d, "u")
+    dev = x0.device
+    dx0, d_w, d_b = out if out is not None else (None, None, None)
+    if dx0 is None:
+        if accumulate:
+            raise RecError("dcn_cross_bwd: accumulate=True needs the buffer to add into as out[0]")
+        dx0 = torch.empty(B, d, dtype=torch.float32, device=dev)
+    ld_dx0 = _dcn_rows(dx0, B, d, "dx0")
+    if d_w is None:
+        d_w = torch.empty(d, dtype=torch.float32, device=dev)
+    if d_b is None:
+        d_b = torch.empty(d, dtype=torch.float32, device=dev)
+    _dcn_vec(d_w, d, "d_w")
+    _dcn_vec(d_b, d, "d_b")
+    if B == 0:
+        d_w.zero_()
+        d_b.zero_()
+    desc = DcnCrossDesc(B, d, L, ld_x0, 0, ld_dxl, ld_dx0, float(l2_coeff), int(bool(accumulate)))
+    nbytes = C.c_size_t(0)
+    check(lib().rec_dcn_cross_bwd_workspace_bytes(C.byref(desc), C.byref(nbytes)), "rec_dcn_cross_bwd_workspace_bytes")
+    wk = ws.get(nbytes.value)
+    check(lib().rec_dcn_cross_bwd(C.byref(desc), _p(x0), _p(w), _p(b), _p(saved), _p(dxl), _p(dz), _p(u), _p(dx0), _p(d_w),
+                                  _p(d_b), _p(wk), C.c_size_t(wk.numel()), _stream()), "rec_dcn_cross_bwd")
+    return dx0, d_w, d_b
 
 
 def dense_fold_fwd(S, dense_w, W0, M):
@@ -1747,15 +1857,15 @@ def gemm(A, B, ws, trans_a=False, trans_b=False, epilogue="none", bias=None, aux
     return out
 
 
-def linear_backward(X, G, W, ws, dW, db, relu_src=None, b_image=None, epilogue=None, aux0=None, relu_bits=None):
+def linear_backward(X, G, W, ws, dW, db, relu_src=None, b_image=None, epilogue=None, aux0=None, relu_bits=None, out=None):
     """The backward of one Linear in ONE call (rec_gemm_f32_pair): dW = X^T G, db = colsum(G) and
     dX = G W^T (masked by relu_src > 0 — the layer's own input — when given; or any dX epilogue of gemm(): epilogue=
     "dsigmoid", aux0=the layer's input).  -> dX.  At launch-bound sizes the two GEMMs are one launch; otherwise exactly the
-    two gemm() calls of mlp_backward, dW first."""
+    two gemm() calls of mlp_backward, dW first.  out: the buffer (view) dX is written to."""
     if epilogue is None:
         epilogue, aux0 = ("relu_mask", relu_src) if relu_src is not None else ("none", None)
     d0, x0, _, need0 = _gemm_prepare(X, G, True, False, "none", None, None, None, dW, 0, db, None, None, 0, None)
-    d1, x1, dX, need1 = _gemm_prepare(G, W, False, True, epilogue, None, aux0, None, None, 0, None, None, None, 0, b_image)
+    d1, x1, dX, need1 = _gemm_prepare(G, W, False, True, epilogue, None, aux0, None, out, 0, None, None, None, 0, b_image)
     if relu_bits is not None and epilogue == "relu_mask":      # relu_src's mask as bits (mlp_forward), where dX has the bit form
         nb = _relu_bits_bytes(d1)
         if nb and relu_bits.numel() * 8 >= nb:
