@@ -24,21 +24,20 @@ import math
 
 import torch
 
-from . import ops
-from .deepfm import NUM_THRESHOLDS, _FlatParams, _OnSide, _round_up, auc_metrics, slot_feeds
+from .deepfm import _FlatParams
+from .slot_net import NUM_THRESHOLDS, SlotDygraphModel, SlotLayerBase, _OnSide, _round_up
 
 L2_COEFF = 1.0      # dygraph_model.py:98: `create_loss(pred, label) + l2_loss`
 
 
-class DeepCroLayer:
+class DeepCroLayer(SlotLayerBase):
     """dcn/net.py:21-158.  forward(sparse_inputs, dense_inputs) -> predict [B,1] (the reference also returns the l2
-    term: forward_with_l2)."""
+    term: forward_with_l2).  grad_dict()'s layer_w / layer_b are summed over the cross layers, the l2 term included."""
     lazy_mode = False   # the dygraph default; the trainer's hyper_parameters.optimizer.lazy_mode sets it
 
     def __init__(self, sparse_feature_number, sparse_feature_dim, dense_feature_dim, sparse_num_field, layer_sizes,
                  cross_num, clip_by_norm=None, l2_reg_cross=None, is_sparse=None, device="cuda", kernels=None):
-        self.device = torch.device(device)
-        self.k = kernels if kernels is not None else ops     # tests may inject a stand-in backend (host logic only)
+        self._init_runtime(device, kernels)
         self.sparse_feature_number = N = sparse_feature_number
         self.sparse_feature_dim = D = sparse_feature_dim
         self.dense_feature_dim = Dn = dense_feature_dim
@@ -70,46 +69,13 @@ class DeepCroLayer:
         for i in range(len(self.layer_sizes)):
             p["linear_%d.weight" % i].normal_(0.0, 1.0 / math.sqrt(sizes[i]))            # net.py:86-90
         p["fc.weight"].normal_(0.0, 1.0 / math.sqrt(H + S + Dn))                         # net.py:100-104
-        self.sparse_state = None
-        self.ws = self.k.Workspace(self.device)
         self.ws_cross = self.k.Workspace(self.device)
-        self.ws_group = self.k.Workspace(self.device)
-        self.status = self.k.new_status(self.device)
-        self.step_count = 0
-        self._side = None
-        self._groups = None
 
     # -- parameters under the reference's state_dict keys ---------------------------------------
     def state_dict(self):
         sd = {"embedding.weight": self.embedding}
         sd.update(self.dense.p)
         return sd
-
-    def set_dict(self, sd):
-        cur = self.state_dict()
-        for k, v in sd.items():
-            dst = cur[k]
-            dst.copy_(torch.as_tensor(v).to(dst.device).reshape(dst.shape))
-
-    def parameters(self):
-        return list(self.state_dict().values())
-
-    def grad_dict(self):
-        """Dense gradients of the last train_step under the reference's parameter names (layer_w / layer_b: summed over
-        the cross layers, the l2 term included)."""
-        return dict(self.dense.g)
-
-    @staticmethod
-    def _concat_ids(sparse_inputs):
-        if isinstance(sparse_inputs, (list, tuple)):
-            return torch.cat(list(sparse_inputs), dim=1).contiguous()        # net.py:108
-        return sparse_inputs
-
-    def _linears(self):
-        n = len(self.layer_sizes)
-        p, g = self.dense.p, self.dense.g
-        return ([p["linear_%d.weight" % i] for i in range(n)], [p["linear_%d.bias" % i] for i in range(n)],
-                [g["linear_%d.weight" % i] for i in range(n)], [g["linear_%d.bias" % i] for i in range(n)])
 
     # -- forward pieces ---------------------------------------------------------------------------
     def _feat(self, ids, dense_inputs):
@@ -132,7 +98,7 @@ class DeepCroLayer:
         feat = self._feat(ids, dense_inputs)
         last_buf = torch.empty(B, _round_up(H + d, 4), dtype=torch.float32, device=self.device)
         last = last_buf[:, :H + d]
-        W, b, _, _ = self._linears()
+        W, b, _, _ = self._linears("linear_%d", len(self.layer_sizes))
         n = len(W)
         acts, x = [], feat
         for i in range(n):                                                   # net.py:147-148: Linear + ReLU each
@@ -145,7 +111,7 @@ class DeepCroLayer:
         return logit, l2, dict(feat=feat, acts=acts, last=last, saved=saved)
 
     def forward(self, sparse_inputs, dense_inputs):
-        ids = self._concat_ids(sparse_inputs)
+        ids = self._concat_ids(sparse_inputs)                                # net.py:108
         logit, _, _ = self._logit(ids, dense_inputs, train=False)
         return torch.sigmoid(logit)                                          # net.py:154
 
@@ -157,13 +123,6 @@ class DeepCroLayer:
         logit, l2, _ = self._logit(ids, dense_inputs, train=True)
         return torch.sigmoid(logit), l2
 
-    def _ensure_sparse_state(self):
-        if self.sparse_state is None:
-            D = self.sparse_feature_dim
-            Dp = _round_up(D, 4)
-            mv = torch.zeros(self.rec.shape[0], _round_up(2 * Dp, 32), dtype=torch.float32, device=self.device)
-            self.sparse_state = dict(mv=mv, m=mv[:, :D], v=mv[:, Dp:Dp + D])
-
     # -- one full training step: train_forward + backward + optimizer.step ----------------------
     def train_step(self, sparse_inputs, dense_inputs, label, lr=1e-3, auc_stats=None):
         """dcn/dygraph_model.py:91-107 + tools/trainer.py backward / step.  label [B,1] int64.
@@ -171,18 +130,8 @@ class DeepCroLayer:
         k, p, g = self.k, self.dense.p, self.dense.g
         ids = self._concat_ids(sparse_inputs)
         B, S = ids.shape
-        D, d, H = self.sparse_feature_dim, self.d, self.layer_sizes[-1]
-        self._ensure_sparse_state()
-        self.step_count += 1
-        t = self.step_count
-        on_gpu = self.device.type == "cuda"
-        cur = torch.cuda.current_stream() if on_gpu else None
-        if on_gpu and self._side is None:
-            self._side = k.concurrent_stream(self.device)
-        side = self._side if on_gpu else None
-        if self._groups is None or self._groups.n != B * S:
-            self._groups = k.IdGroups(B * S, self.device)
-        groups = self._groups
+        d, H = self.d, self.layer_sizes[-1]
+        t, cur, side, groups = self._begin_step(B * S)
         with _OnSide(side, cur):                                   # the merge keys depend on the ids only
             k.ids_group(ids, self.sparse_feature_number, self.padding_idx, self.ws_group, None, self.status, groups)
         logit, l2, sv = self._logit(ids, dense_inputs, train=True)
@@ -197,8 +146,8 @@ class DeepCroLayer:
         fcw = p["fc.weight"]
         k.gemm(last, dz, self.ws, trans_a=True, out=g["fc.weight"], b_colsum=g["fc.bias"])
         gy = k.gemm(dz, fcw[:H], self.ws, trans_b=True, epilogue="relu_mask", aux0=last[:, :H])
-        W, _, dW, db = self._linears()
-        dfeat_buf = self._dfeat_buf(B)
+        W, _, dW, db = self._linears("linear_%d", len(self.layer_sizes))
+        dfeat_buf = self._buf("_dfeat", (B, self.d_pad))
         dfeat = dfeat_buf[:, :d]
         for i in reversed(range(len(W))):
             gy = k.linear_backward(acts[i], gy, W[i], self.ws, dW[i], db[i], relu_src=acts[i] if i > 0 else None,
@@ -206,26 +155,15 @@ class DeepCroLayer:
         k.dcn_cross_bwd(feat, p["layer_w"], p["layer_b"], sv["saved"], None, self.ws_cross, l2_coeff=L2_COEFF,
                         accumulate=True, out=(dfeat, g["layer_w"], g["layer_b"]), dz=dz, u=fcw[H:].reshape(-1))
         st = self.sparse_state
-        with _OnSide(side, cur):
-            layout = dict(grad_group=S, grad_group_stride=self.d_pad)         # lookup (b, s) = dfeat[b, s*D : (s+1)*D]
-            pp = self._pp = k.segment_partials(groups, dfeat_buf, D, out=getattr(self, "_pp", None), **layout)
-            upd = k.sparse_adam_rows if self.lazy_mode else k.adam_rows_all
-            upd(groups, dfeat_buf, 1, self.embedding, st["m"], st["v"], t, lr, partials=pp, **layout)
-        k.adam_dense(self.dense.data, self.dense.m, self.dense.v, self.dense.grad, t, lr)
-        if on_gpu:
-            cur.wait_stream(self._side)
+        self._update_rows(t, lr, cur, side, (groups, dfeat_buf, 1, self.embedding, st["m"], st["v"]),
+                          grad_group=S, grad_group_stride=self.d_pad)     # lookup (b, s) = dfeat[b, s*D : (s+1)*D]
+        self._finish_step(t, lr, cur, side)
         self._last_dfeat = dfeat
         return loss, pred
 
-    def _dfeat_buf(self, B):
-        b = getattr(self, "_dfeat", None)
-        if b is None or b.shape[0] != B:
-            self._dfeat = torch.empty(B, self.d_pad, dtype=torch.float32, device=self.device)
-        return self._dfeat
 
-
-class DygraphModel:
-    """dcn/dygraph_model.py:22-120 — same method names; tensors are torch device tensors."""
+class DygraphModel(SlotDygraphModel):
+    """dcn/dygraph_model.py:22-120."""
 
     def create_model(self, config, device="cuda", kernels=None):
         g = config.get
@@ -234,23 +172,3 @@ class DygraphModel:
                             g("hyper_parameters.fc_sizes"), g("hyper_parameters.cross_num"),
                             g("hyper_parameters.clip_by_norm", None), g("hyper_parameters.l2_reg_cross", None),
                             g("hyper_parameters.is_sparse", None), device=device, kernels=kernels)
-
-    def create_feeds(self, batch_data, config, device="cuda"):
-        return slot_feeds(batch_data, config, device)
-
-    def create_metrics(self, device="cuda"):
-        return auc_metrics(device)
-
-    def train_forward(self, dy_model, metrics_list, batch_data, config):
-        label, sparse, dense = self.create_feeds(batch_data, config, dy_model.device)
-        lr = config.get("hyper_parameters.optimizer.learning_rate", 0.001)
-        loss, _ = dy_model.train_step(sparse, dense, label, lr, metrics_list[0] if metrics_list else None)
-        return loss, metrics_list, None
-
-    def infer_forward(self, dy_model, metrics_list, batch_data, config):
-        label, sparse, dense = self.create_feeds(batch_data, config, dy_model.device)
-        pred = dy_model.forward(sparse, dense)
-        if metrics_list:
-            dy_model.k.auc_histogram(pred.contiguous(), label.contiguous(), metrics_list[0][0], metrics_list[0][1],
-                                     NUM_THRESHOLDS)
-        return metrics_list, None

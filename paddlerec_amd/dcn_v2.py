@@ -23,12 +23,13 @@ import torch
 
 from . import ops
 from . import ops as _ops
-from .deepfm import NUM_THRESHOLDS, _FlatParams, _round_up, _Timed, auc_metrics, slot_feeds
+from .deepfm import _FlatParams, _Timed
+from .slot_net import NUM_THRESHOLDS, SlotDygraphModel, SlotLayerBase, _round_up
 
 P = "DeepCrossLayer_.crossNet."
 
 
-class DCN_V2Layer:
+class DCN_V2Layer(SlotLayerBase):
     """dcn_v2/net.py:20-137.  forward(sparse_inputs, dense_inputs) -> predict [B,1]."""
 
     def __init__(self, sparse_feature_number, sparse_feature_dim, dense_feature_dim, sparse_num_field,
@@ -113,12 +114,6 @@ class DCN_V2Layer:
                 sd[k] = v
         return sd
 
-    def set_dict(self, sd):
-        cur = self.state_dict()
-        for k, v in sd.items():
-            dst = cur[k]
-            dst.copy_(torch.as_tensor(v).to(dst.device).reshape(dst.shape))
-
     def grad_dict(self):
         """Dense gradients of the last train_step under the reference's parameter names."""
         out = {}
@@ -135,12 +130,6 @@ class DCN_V2Layer:
 
     def _timed(self, name):
         return _Timed(self.timers, name)
-
-    @staticmethod
-    def _concat_ids(sparse_inputs):
-        if isinstance(sparse_inputs, (list, tuple)):
-            return torch.cat(list(sparse_inputs), dim=1).contiguous()       # net.py:93-94
-        return sparse_inputs
 
     # ---------------------------------------------------------------- forward pieces
     def _feat(self, ids, dense_inputs):
@@ -251,20 +240,13 @@ class DCN_V2Layer:
         return (logit, saved) if keep else (logit, None)
 
     def forward(self, sparse_inputs, dense_inputs):
-        ids = self._concat_ids(sparse_inputs)
+        ids = self._concat_ids(sparse_inputs)                                             # net.py:93-94
         logit, _ = self._logit(ids, dense_inputs)
         return torch.sigmoid(logit)                                                       # net.py:117,134
 
     __call__ = forward
 
     # ---------------------------------------------------------------- training step (CrossNetV2)
-    def _ensure_sparse_state(self):
-        if self.sparse_state is None:
-            D = self.sparse_feature_dim
-            Dp = _round_up(D, 4)
-            mv = torch.zeros(self.rec.shape[0], _round_up(2 * Dp, 32), dtype=torch.float32, device=self.device)
-            self.sparse_state = dict(mv=mv, m=mv[:, :D], v=mv[:, Dp:Dp + D])
-
     def train_step(self, sparse_inputs, dense_inputs, label, lr=1e-3, clip_norm=10.0, auc_stats=None,
                    dlogit=None):
         """dcn_v2/dygraph_model.py:103-127 train_forward + backward + Adam with ClipGradByGlobalNorm.
@@ -476,8 +458,8 @@ class DCN_V2Layer:
         return b
 
 
-class DygraphModel:
-    """dcn_v2/dygraph_model.py:24-140 — same method names; tensors are torch device tensors."""
+class DygraphModel(SlotDygraphModel):
+    """dcn_v2/dygraph_model.py:24-140."""
 
     def create_model(self, config, device="cuda", kernels=None):
         g = config.get
@@ -492,23 +474,9 @@ class DygraphModel:
                            dropout_rate=g("hyper_parameters.dropout_rate", 0.5), l2_dnn=1e-7,
                            dropout_seed=g("runner.seed", 12345))
 
-    def create_feeds(self, batch_data, config, device="cuda"):
-        return slot_feeds(batch_data, config, device)
-
-    def create_metrics(self, device="cuda"):
-        return auc_metrics(device)
-
     def train_forward(self, dy_model, metrics_list, batch_data, config):
         label, sparse, dense = self.create_feeds(batch_data, config, dy_model.device)
         lr = config.get("hyper_parameters.optimizer.learning_rate", 0.001)
         clip = config.get("hyper_parameters.optimizer.clip_by_norm", 10.0)        # dygraph_model.py:83-85
         loss, _ = dy_model.train_step(sparse, dense, label, lr, clip, metrics_list[0] if metrics_list else None)
         return loss, metrics_list, {"log_loss": loss}
-
-    def infer_forward(self, dy_model, metrics_list, batch_data, config):
-        label, sparse, dense = self.create_feeds(batch_data, config, dy_model.device)
-        pred = dy_model.forward(sparse, dense)
-        if metrics_list:
-            dy_model.k.auc_histogram(pred.contiguous(), label.contiguous(), metrics_list[0][0], metrics_list[0][1],
-                                     NUM_THRESHOLDS)
-        return metrics_list, None

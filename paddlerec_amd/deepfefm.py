@@ -23,22 +23,23 @@ import math
 
 import torch
 
-from . import ops
-from .deepfm import NUM_THRESHOLDS, _FlatParams, _OnSide, auc_metrics, slot_feeds
+from .deepfm import _FlatParams
+from .slot_net import NUM_THRESHOLDS, SlotDygraphModel, SlotLayerBase, _OnSide, _round_up
 
 L2_EMB = 1e-6       # net.py:77,90,96
 L2_DNN = 1e-7       # net.py:111,219
 FE_KEY = "fefm.field_embeddings"
 
 
-class DeepFEFMLayer:
-    """deepfefm/net.py:23-52.  forward(sparse_inputs, dense_inputs) -> predict [B,1] (eval mode: no dropout)."""
+class DeepFEFMLayer(SlotLayerBase):
+    """deepfefm/net.py:23-52.  forward(sparse_inputs, dense_inputs) -> predict [B,1] (eval mode: no dropout).
+    set_dict with a dict without `fefm.field_embeddings` (a checkpoint of the reference) keeps the current matrices;
+    grad_dict()'s gradients include the L2 terms."""
     lazy_mode = False   # the dygraph default; the trainer's hyper_parameters.optimizer.lazy_mode sets it
 
     def __init__(self, sparse_feature_number, sparse_feature_dim, dense_feature_dim, sparse_num_field, layer_sizes,
                  device="cuda", kernels=None, dropout_rate=0.0, dropout_seed=2025, train_field_embeddings=False):
-        self.device = torch.device(device)
-        self.k = kernels if kernels is not None else ops     # tests may inject a stand-in backend (host logic only)
+        self._init_runtime(device, kernels)
         self.sparse_feature_number = N = sparse_feature_number
         self.sparse_feature_dim = D = sparse_feature_dim
         self.dense_feature_dim = Dn = dense_feature_dim
@@ -49,7 +50,7 @@ class DeepFEFMLayer:
         self.num_fields = F = S + Dn
         self.num_pairs = P = F * (F - 1) // 2
         self.input_size = S * D + Dn + P                                     # net.py:205-207
-        self.row_pad = (D + 3) // 4 * 4
+        self.row_pad = _round_up(D, 4)
         std = 0.1 / math.sqrt(float(D))                                      # net.py:64-116 TruncatedNormal
         f32 = dict(dtype=torch.float32, device=self.device)
         self.emb_table = torch.zeros(N, self.row_pad, **f32)
@@ -69,14 +70,7 @@ class DeepFEFMLayer:
         torch.nn.init.trunc_normal_(p[FE_KEY], 0.0, std, -2 * std, 2 * std)
         for i in range(len(sizes) - 1):
             p["dnn.linear_%d.weight" % i].normal_(0.0, 1.0 / math.sqrt(sizes[i]))   # net.py:220-221
-        self.sparse_state = None
-        self.ws = self.k.Workspace(self.device)
         self.ws_fefm = self.k.Workspace(self.device)
-        self.ws_group = self.k.Workspace(self.device)
-        self.status = self.k.new_status(self.device)
-        self.step_count = 0
-        self._side = None
-        self._groups = self._groups1 = None
 
     # -- parameters under the reference's state_dict keys (+ fefm.field_embeddings) ---------------
     def state_dict(self):
@@ -84,38 +78,12 @@ class DeepFEFMLayer:
         sd.update(self.dense.p)
         return sd
 
-    def set_dict(self, sd):
-        """A dict without `fefm.field_embeddings` (a checkpoint of the reference) keeps the current matrices."""
-        cur = self.state_dict()
-        for k, v in sd.items():
-            dst = cur[k]
-            dst.copy_(torch.as_tensor(v).to(dst.device).reshape(dst.shape))
-
-    def parameters(self):
-        return list(self.state_dict().values())
-
-    def grad_dict(self):
-        """Dense gradients of the last train_step under the parameter names (L2 terms included)."""
-        return dict(self.dense.g)
-
-    @staticmethod
-    def _concat_ids(sparse_inputs):
-        if isinstance(sparse_inputs, (list, tuple)):
-            return torch.cat(list(sparse_inputs), dim=1).contiguous()        # net.py:120-121
-        return sparse_inputs
-
-    def _linears(self):
-        n = len(self.layer_sizes) + 1
-        p, g = self.dense.p, self.dense.g
-        return ([p["dnn.linear_%d.weight" % i] for i in range(n)], [p["dnn.linear_%d.bias" % i] for i in range(n)],
-                [g["dnn.linear_%d.weight" % i] for i in range(n)], [g["dnn.linear_%d.bias" % i] for i in range(n)])
-
     def _fefm(self, ids, dense_inputs):
         """rec_fefm_fwd writes the MLP's input in place: a [B, input_size] view of rows padded to 4 floats."""
         p = self.dense.p
         B = ids.shape[0]
         f32 = dict(dtype=torch.float32, device=self.device)
-        buf = torch.empty(B, (self.input_size + 3) // 4 * 4, **f32)
+        buf = torch.empty(B, _round_up(self.input_size, 4), **f32)
         out = (torch.empty(B, 1, **f32), torch.empty(B, 1, **f32), buf[:, :self.input_size],
                torch.empty(B, self.num_fields, dtype=torch.int64, device=self.device))
         return self.k.fefm_fwd(ids, dense_inputs, self.emb_table, self.embedding_one, p["fefm.dense_w_one"], p[FE_KEY],
@@ -124,7 +92,7 @@ class DeepFEFMLayer:
     def forward(self, sparse_inputs, dense_inputs):
         ids = self._concat_ids(sparse_inputs)
         y1, y2, dnn_in, _, _ = self._fefm(ids, dense_inputs)
-        W, b, _, _ = self._linears()
+        W, b, _, _ = self._linears("dnn.linear_%d", len(self.layer_sizes) + 1)
         y_dnn, _ = self.k.mlp_forward(dnn_in, W, b, self.ws)
         return torch.sigmoid(y1 + y2 + y_dnn)
 
@@ -132,9 +100,7 @@ class DeepFEFMLayer:
 
     def _ensure_sparse_state(self):
         if self.sparse_state is None:
-            N, Dp = self.emb_table.shape
-            z = lambda w: torch.zeros(N, w, dtype=torch.float32, device=self.device)
-            self.sparse_state = dict(m=z(Dp), v=z(Dp), m1=z(1), v1=z(1))
+            self.sparse_state = self._separate_moments(*self.emb_table.shape)
 
     def _drop(self):
         return self.dropout_rate > 0.0
@@ -144,28 +110,18 @@ class DeepFEFMLayer:
         """deepfefm/dygraph_model.py train_forward + tools/trainer.py backward / step.  label [B,1] int64.
         Returns (loss [1] device tensor, pred [B,1])."""
         k, p, g = self.k, self.dense.p, self.dense.g
-        ids = self._concat_ids(sparse_inputs)
+        ids = self._concat_ids(sparse_inputs)                      # net.py:120-121
         B, S = ids.shape
         D, F = self.sparse_feature_dim, self.num_fields
-        self._ensure_sparse_state()
-        self.step_count += 1
-        t = self.step_count
-        on_gpu = self.device.type == "cuda"
-        cur = torch.cuda.current_stream() if on_gpu else None
-        if on_gpu and self._side is None:
-            self._side = k.concurrent_stream(self.device)
-        side = self._side if on_gpu else None
-        if self._groups is None or self._groups.n != B * F:
-            self._groups, self._groups1 = k.IdGroups(B * F, self.device), k.IdGroups(B * S, self.device)
-        groups, groups1 = self._groups, self._groups1
+        t, cur, side, (groups, groups1) = self._begin_step(B * F, B * S)
         y1, y2, dnn_in, ids_all, _ = self._fefm(ids, dense_inputs)
         with _OnSide(side, cur):                                   # merge keys: the table's are ids_all, W1's the sparse ids
             k.ids_group(ids_all, self.sparse_feature_number, 0, self.ws_group, None, self.status, groups)
             k.ids_group(ids, self.sparse_feature_number, 0, self.ws_group, None, self.status, groups1)
         # DNN.forward (net.py:229-234): Dropout after every element of _mlp_layers; relu(drop(z)) = drop(relu(z)), so a
         # hidden layer is the GEMM's bias+ReLU epilogue followed by ONE dropout pass with two mask streams
-        W, b, dW, db = self._linears()
         n = len(self.layer_sizes)
+        W, b, dW, db = self._linears("dnn.linear_%d", n + 1)
         drop, rate, seed = self._drop(), self.dropout_rate, self.dropout_seed
         nstreams = 2 * n + 1
         base = t * nstreams
@@ -198,14 +154,11 @@ class DeepFEFMLayer:
         tfe = self.train_field_embeddings
         row_grad, _, _ = k.fefm_bwd(ids_all, dense_inputs, self.emb_table, p[FE_KEY], dz, d_dnn_in, S, D, self.ws_fefm,
                                     want_d_fe=tfe, status=self.status,
-                                    out=(self._row_grad_buf(B * F), g["fefm.dense_w_one"], g[FE_KEY] if tfe else None))
+                                    out=(self._buf("_rg", (B * F, self.row_pad)), g["fefm.dense_w_one"],
+                                         g[FE_KEY] if tfe else None))
         st = self.sparse_state
-        with _OnSide(side, cur):
-            upd = k.sparse_adam_rows if self.lazy_mode else k.adam_rows_all
-            pp = self._pp = k.segment_partials(groups, row_grad, self.row_pad, out=getattr(self, "_pp", None))
-            pp1 = self._pp1 = k.segment_partials(groups1, dz, 1, grad_div=S, out=getattr(self, "_pp1", None))
-            upd(groups, row_grad, 1, self.emb_table, st["m"], st["v"], t, lr, partials=pp, l2=L2_EMB)
-            upd(groups1, dz, S, self.embedding_one, st["m1"], st["v1"], t, lr, partials=pp1, l2=L2_EMB)
+        self._update_rows(t, lr, cur, side, (groups, row_grad, 1, self.emb_table, st["m"], st["v"]),
+                          (groups1, dz, S, self.embedding_one, st["m1"], st["v1"]), l2=L2_EMB)
         k.l2_decay_grad(g["fefm.dense_w_one"], p["fefm.dense_w_one"], L2_EMB)
         for i in range(n + 1):
             k.l2_decay_grad(dW[i].reshape(-1), W[i].reshape(-1), L2_DNN)
@@ -214,23 +167,13 @@ class DeepFEFMLayer:
         # `bias` keeps a zero gradient and zero moments: Adam moves it by exactly 0.  The pair matrices are the LAST tensor of
         # the flat buffer: frozen, the Adam launch stops in front of them (no pass over them, and moments loaded from a
         # checkpoint of a run that trained them cannot move them)
-        d = self.dense
-        n_adam = d.data.numel() if tfe else d.offsets[FE_KEY]
-        k.adam_dense(d.data[:n_adam], d.m[:n_adam], d.v[:n_adam], d.grad[:n_adam], t, lr)
-        if on_gpu:
-            cur.wait_stream(self._side)
+        self._finish_step(t, lr, cur, side, n_adam=self.dense.data.numel() if tfe else self.dense.offsets[FE_KEY])
         self._last = dict(row_grad=row_grad, ids_all=ids_all, dz=dz)
         return loss, pred
 
-    def _row_grad_buf(self, n):
-        b = getattr(self, "_rg", None)
-        if b is None or b.shape[0] != n:
-            self._rg = torch.empty(n, self.row_pad, dtype=torch.float32, device=self.device)
-        return self._rg
 
-
-class DygraphModel:
-    """deepfefm/dygraph_model.py — same method names; tensors are torch device tensors."""
+class DygraphModel(SlotDygraphModel):
+    """deepfefm/dygraph_model.py."""
 
     def create_model(self, config, device="cuda", kernels=None):
         g = config.get
@@ -240,23 +183,3 @@ class DygraphModel:
                              dropout_rate=0.2,                       # the DNN constructor's default (net.py:197), no YAML key
                              dropout_seed=g("runner.seed", 12345),
                              train_field_embeddings=bool(g("hyper_parameters.train_field_embeddings", False)))
-
-    def create_feeds(self, batch_data, config, device="cuda"):
-        return slot_feeds(batch_data, config, device)
-
-    def create_metrics(self, device="cuda"):
-        return auc_metrics(device)
-
-    def train_forward(self, dy_model, metrics_list, batch_data, config):
-        label, sparse, dense = self.create_feeds(batch_data, config, dy_model.device)
-        lr = config.get("hyper_parameters.optimizer.learning_rate", 0.001)
-        loss, _ = dy_model.train_step(sparse, dense, label, lr, metrics_list[0] if metrics_list else None)
-        return loss, metrics_list, None
-
-    def infer_forward(self, dy_model, metrics_list, batch_data, config):
-        label, sparse, dense = self.create_feeds(batch_data, config, dy_model.device)
-        pred = dy_model.forward(sparse, dense)
-        if metrics_list:
-            dy_model.k.auc_histogram(pred.contiguous(), label.contiguous(), metrics_list[0][0], metrics_list[0][1],
-                                     NUM_THRESHOLDS)
-        return metrics_list, None

@@ -17,8 +17,8 @@ import time
 import torch
 
 from . import ops
-
-NUM_THRESHOLDS = 4095  # paddle.metric.Auc default [EXT]
+from .slot_net import (NUM_THRESHOLDS, SlotDygraphModel, SlotLayerBase, _OnSide, _round_up,  # noqa: F401 (re-exported)
+                       auc_metrics, slot_feeds)
 
 
 class _FlatParams:
@@ -89,28 +89,6 @@ class _Timed:
             self.timers.setdefault(self.name + "@host", []).append(time.perf_counter() - self.h0)
 
 
-class _OnSide:
-    """`with _OnSide(side, cur):` — issue on the side stream, ordered after everything issued so far on `cur`.
-    side None (a CPU device: orchestration tests with an injected operator backend) makes it a no-op."""
-
-    def __init__(self, side, cur):
-        self.side, self.cur = side, cur
-
-    def __enter__(self):
-        if self.side is not None:
-            self.side.wait_stream(self.cur)
-            self.ctx = torch.cuda.stream(self.side)
-            self.ctx.__enter__()
-
-    def __exit__(self, *a):
-        if self.side is not None:
-            self.ctx.__exit__(*a)
-
-
-def _round_up(x, m):
-    return (x + m - 1) // m * m
-
-
 class FM:
     """net.py:52-139.  Holds embedding_one [N,1], embedding [N,D]; dense_w_one/dense_w live in the
     flat dense buffer of the owning DeepFMLayer."""
@@ -157,7 +135,7 @@ class FM:
                 t[self.padding_idx].zero_()                    # padding row zeroed at construction [EXT]
 
 
-class DeepFMLayer:
+class DeepFMLayer(SlotLayerBase):
     """net.py:21-49.  forward(sparse_inputs, dense_inputs) -> predict [B,1]."""
 
     def __init__(self, sparse_feature_number, sparse_feature_dim, dense_feature_dim,
@@ -271,21 +249,7 @@ class DeepFMLayer:
         sd.update({k: v for k, v in self.dense.p.items() if not k.startswith("__")})
         return sd
 
-    def set_dict(self, sd):
-        for k, v in sd.items():
-            dst = self.state_dict()[k]
-            dst.copy_(torch.as_tensor(v).to(dst.device).reshape(dst.shape))
-
-    def parameters(self):
-        return list(self.state_dict().values())
-
     # -- forward (net.py:41-49) -----------------------------------------------------------------
-    @staticmethod
-    def _concat_ids(sparse_inputs):
-        if isinstance(sparse_inputs, (list, tuple)):
-            return torch.cat(list(sparse_inputs), dim=1).contiguous()       # net.py:107
-        return sparse_inputs
-
     def _fm_fwd(self, ids, dense_inputs):
         if self.padded:
             B, dev = ids.shape[0], self.device
@@ -386,7 +350,7 @@ class DeepFMLayer:
 
     def forward(self, sparse_inputs, dense_inputs):
         self.sync()
-        ids = self._concat_ids(sparse_inputs)
+        ids = self._concat_ids(sparse_inputs)                               # net.py:107
         y1, y2, feat, _, _ = self._fm_fwd(ids, dense_inputs)
         y_dnn, _ = self.k.mlp_forward(feat.view(feat.shape[0], -1), self._mlp_weights()[0], self.mlp_b, self.ws_mlp)
         return torch.sigmoid(y1 + y2 + y_dnn)
@@ -652,7 +616,7 @@ class DeepFMLayer:
         with self._timed("fm_bwd"):
             row_grad, _, _ = self.k.deepfm_fm_bwd(
                 dense_inputs, feat, sum_emb, d_flat if self.padded else d_flat.view(B, self.fp, -1), dz, dz, S, self.ws,
-                out=(self._row_grad_buf(B * S),
+                out=(self._buf("_rg", (B * S, self.sparse_feature_dim)),
                      self.dense.g["fm.dense_w"].view(self.dense_feature_dim, -1),
                      self.dense.g["fm.dense_w_one"]),
                 dense_w=self.dense.p["fm.dense_w"], compact=self.compact,
@@ -765,7 +729,7 @@ class DeepFMLayer:
         dfeat = torch.randn(*((B, self.ld0) if self.padded else (B, self.fp, D)), device=self.device) * 1e-3
         pkw = dict(feat_ld=self.ld0) if self.padded else {}
         dz = torch.randn(B, 1, device=self.device) * 1e-3
-        out = (self._row_grad_buf(B * S), torch.empty(self.dense_feature_dim, D, device=self.device),
+        out = (self._buf("_rg", (B * S, D)), torch.empty(self.dense_feature_dim, D, device=self.device),
                torch.empty(self.dense_feature_dim, device=self.device))
 
         def fwd(i):
@@ -797,37 +761,8 @@ class DeepFMLayer:
             return sorted(ts)[len(ts) // 2]
         return run(fwd), run(bwd)
 
-    def _row_grad_buf(self, n):
-        b = getattr(self, "_rg", None)
-        if b is None or b.shape[0] != n:
-            self._rg = torch.empty(n, self.sparse_feature_dim, dtype=torch.float32, device=self.device)
-        return self._rg
-
-
-def slot_feeds(batch_data, config, device):
-    """create_feeds of the Criteo slot models (deepfm/dygraph_model.py:41-51, same code in fm / wide_deep / dcn_v2):
-    -> (label [B,1] i64, sparse, dense [B,Dn] f32) on `device`.  batch_data is either the reference's 28 arrays
-    [label, C1..C26, dense] (sparse = list of 26 [B,1] tensors) or the (label [B,1], ids [B,26], dense [B,13]) device
-    tensors of paddlerec_amd.reader (sparse = the [B,26] tensor: no per-slot split and re-concat)."""
-    if len(batch_data) == 3 and torch.is_tensor(batch_data[1]) and batch_data[1].dim() == 2 \
-            and batch_data[1].shape[1] > 1:
-        label, ids, dense = batch_data
-        return label.to(device), ids.to(device), dense.to(device)
-    dn = config.get("hyper_parameters.dense_input_dim")
-    sparse = [torch.as_tensor(b).to(torch.int64).reshape(-1, 1).to(device) for b in batch_data[:-1]]
-    dense = torch.as_tensor(batch_data[-1]).to(torch.float32).reshape(-1, dn).to(device)
-    return sparse[0], sparse[1:], dense
-
-
-def auc_metrics(device):
-    """create_metrics: paddle.metric.Auc("ROC") = the two int64 bucket arrays of rec_auc_histogram, on the device."""
-    stats = (torch.zeros(NUM_THRESHOLDS + 1, dtype=torch.int64, device=device),
-             torch.zeros(NUM_THRESHOLDS + 1, dtype=torch.int64, device=device))
-    return [stats], ["auc"]
-
-
-class DygraphModel:
-    """deepfm/dygraph_model.py:23-98 — same method names; tensors are torch device tensors."""
+class DygraphModel(SlotDygraphModel):
+    """deepfm/dygraph_model.py:23-98."""
 
     def create_model(self, config, device="cuda", kernels=None, comm=None):
         """comm (paddlerec_amd.sharded.Comm, world > 1): the row-sharded layer of the collective mode."""
@@ -839,12 +774,6 @@ class DygraphModel:
             return ShardedDeepFMLayer(*args, device=device, comm=comm, kernels=kernels)
         return DeepFMLayer(*args, device=device, kernels=kernels)
 
-    def create_feeds(self, batch_data, config, device="cuda"):
-        return slot_feeds(batch_data, config, device)
-
-    def create_metrics(self, device="cuda"):
-        return auc_metrics(device)
-
     def train_forward(self, dy_model, metrics_list, batch_data, config, lr=None, next_batch=None):
         """next_batch (row-sharded layer only): the batch the next call will get — its ids are routed a step ahead."""
         label, sparse, dense = self.create_feeds(batch_data, config, dy_model.device)
@@ -854,15 +783,6 @@ class DygraphModel:
             kw["next_sparse_inputs"] = self.create_feeds(next_batch, config, dy_model.device)[1]
         loss, _ = dy_model.train_step(sparse, dense, label, lr, metrics_list[0] if metrics_list else None, **kw)
         return loss, metrics_list, {"loss": loss}
-
-    def infer_forward(self, dy_model, metrics_list, batch_data, config):
-        label, sparse, dense = self.create_feeds(batch_data, config, dy_model.device)
-        pred = dy_model.forward(sparse, dense)
-        if metrics_list:
-            dy_model.k.auc_histogram(pred.contiguous(), label.contiguous(), metrics_list[0][0],
-                                     metrics_list[0][1], NUM_THRESHOLDS)
-        return metrics_list, None
-
 
 def auc_from_buckets(stat_pos, stat_neg):
     """tools/utils/utils_single.py:183-204 — trapezoid sweep from the top bucket (host, fp64)."""

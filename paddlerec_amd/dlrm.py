@@ -23,21 +23,20 @@ import math
 
 import torch
 
-from . import ops
-from .deepfm import NUM_THRESHOLDS, _FlatParams, _OnSide, _round_up, auc_from_buckets, auc_metrics, slot_feeds
+from .deepfm import _FlatParams, auc_from_buckets
+from .slot_net import NUM_THRESHOLDS, SlotDygraphModel, SlotLayerBase, _OnSide, _round_up, auc_metrics
 
 BN_MOMENTUM, BN_EPS = 0.9, 1e-5       # paddle.nn.BatchNorm1D defaults [EXT]
 
 
-class DLRMLayer:
+class DLRMLayer(SlotLayerBase):
     """dlrm/net.py:23-125.  forward(sparse_inputs, dense_inputs) -> raw [B,2] (unnormalised class scores)."""
 
     def __init__(self, dense_feature_dim, bot_layer_sizes, sparse_feature_number, sparse_feature_dim, top_layer_sizes,
                  num_field, sync_mode=None, self_interaction=False, device="cuda", kernels=None):
         if self_interaction:
             raise NotImplementedError("self_interaction=True (the reference's dygraph_model.py passes False)")
-        self.device = torch.device(device)
-        self.k = kernels if kernels is not None else ops
+        self._init_runtime(device, kernels)
         self.dense_feature_dim, self.sparse_feature_number = dense_feature_dim, sparse_feature_number
         self.sparse_feature_dim = D = sparse_feature_dim
         self.num_field = S = num_field
@@ -67,17 +66,11 @@ class DLRMLayer:
                 self.dense.p["%s.norm_%d.weight" % (name, i)].fill_(1.0)
                 self.buffers["%s.norm_%d._mean" % (name, i)] = torch.zeros(sizes[i + 1], device=self.device)
                 self.buffers["%s.norm_%d._variance" % (name, i)] = torch.ones(sizes[i + 1], device=self.device)
-        self.sparse_state = None
-        self.ws = self.k.Workspace(self.device)
-        self.ws_group = self.k.Workspace(self.device)
         self.ws_bn = self.k.Workspace(self.device)
-        self.status = self.k.new_status(self.device)
         self._diff = torch.tensor([[-1.0], [1.0]], dtype=torch.float32, device=self.device)     # raw -> raw1 - raw0
         self._diff_t = self._diff.t().contiguous()
-        self.step_count = 0
         self.training = True
-        self._side = None
-        self._groups = None
+        self.lazy_mode = False      # the reference's Adam(parameters=...): every row's moments move each step
 
     # -- parameters under the reference's state_dict keys ---------------------------------------
     def state_dict(self):
@@ -86,25 +79,14 @@ class DLRMLayer:
         sd.update(self.buffers)
         return sd
 
-    def set_dict(self, sd):
-        cur = self.state_dict()
-        for k, v in sd.items():
-            cur[k].copy_(torch.as_tensor(v).to(self.device).reshape(cur[k].shape))
-
     def parameters(self):
-        return [self.embedding] + list(self.dense.p.values())
+        return [self.embedding] + list(self.dense.p.values())       # the running statistics are buffers
 
     def train(self):
         self.training = True
 
     def eval(self):
         self.training = False
-
-    @staticmethod
-    def _concat_ids(sparse_inputs):
-        if isinstance(sparse_inputs, (list, tuple)):
-            return torch.cat(list(sparse_inputs), dim=1).contiguous()
-        return sparse_inputs
 
     # -- MLP of Linear -> ReLU -> BatchNorm layers ------------------------------------------------
     def _mlp_forward(self, name, x, training, out_last=None):
@@ -157,29 +139,13 @@ class DLRMLayer:
         """softmax(raw)[:, 1:2] (dygraph_model.py:78) = sigmoid(raw1 - raw0)."""
         return torch.sigmoid(self.k.gemm(raw, self._diff, self.ws))
 
-    def _ensure_sparse_state(self):
-        if self.sparse_state is None:
-            D = self.sparse_feature_dim
-            Dp = _round_up(D, 4)
-            mv = torch.zeros(self.rec.shape[0], _round_up(2 * Dp, 32), dtype=torch.float32, device=self.device)
-            self.sparse_state = dict(mv=mv, m=mv[:, :D], v=mv[:, Dp:Dp + D])
-
     def train_step(self, sparse_inputs, dense_inputs, label, lr=1e-3, auc_stats=None, acc_counts=None):
         """dlrm/dygraph_model.py:74-91 + tools/trainer.py:148-152.  label [B,1] int64.
         Returns (loss [1] device tensor, pred [B,1] = P(click))."""
         k, D = self.k, self.sparse_feature_dim
         ids = self._concat_ids(sparse_inputs)
         B, S = ids.shape
-        self._ensure_sparse_state()
-        self.step_count += 1
-        on_gpu = self.device.type == "cuda"
-        cur = torch.cuda.current_stream() if on_gpu else None
-        if on_gpu and self._side is None:
-            self._side = k.concurrent_stream(self.device)
-        side = self._side if on_gpu else None
-        if self._groups is None or self._groups.n != B * S:
-            self._groups = k.IdGroups(B * S, self.device)
-        groups = self._groups
+        t, cur, side, groups = self._begin_step(B * S)
         sv = {}
         raw = self._forward(ids, dense_inputs, True, keep=sv)
         with _OnSide(side, cur):                                   # merge keys depend on the ids only
@@ -195,20 +161,15 @@ class DLRMLayer:
         dT = k.dot_interact_bwd(sv["T"], dR)                                               # [B,S+1,D]
         dflat = dT.view(B, (S + 1) * D)
         self._mlp_backward("bot_mlp", dflat[:, S * D:], sv["cb"])
-        t, st = self.step_count, self.sparse_state
-        with _OnSide(side, cur):   # non-lazy Adam: every row's moments move; touched rows get their merged gradient
-            pp = self._pp = k.segment_partials(groups, dflat, D, grad_group=S, grad_group_stride=(S + 1) * D,
-                                               out=getattr(self, "_pp", None))
-            k.adam_rows_all(groups, dflat, 1, self.embedding, st["m"], st["v"], t, lr, grad_group=S,
-                            grad_group_stride=(S + 1) * D, partials=pp)
-        k.adam_dense(self.dense.data, self.dense.m, self.dense.v, self.dense.grad, t, lr)
-        if on_gpu:
-            cur.wait_stream(self._side)
+        st = self.sparse_state     # non-lazy Adam: every row's moments move; touched rows get their merged gradient
+        self._update_rows(t, lr, cur, side, (groups, dflat, 1, self.embedding, st["m"], st["v"]),
+                          grad_group=S, grad_group_stride=(S + 1) * D)
+        self._finish_step(t, lr, cur, side)
         return loss, pred
 
 
-class DygraphModel:
-    """dlrm/dygraph_model.py:23-107 — same method names; tensors are torch device tensors."""
+class DygraphModel(SlotDygraphModel):
+    """dlrm/dygraph_model.py:23-107."""
 
     def create_model(self, config, device="cuda", kernels=None):
         g = config.get
@@ -219,9 +180,6 @@ class DygraphModel:
                          top_layer_sizes=g("hyper_parameters.top_layer_sizes"),
                          num_field=g("hyper_parameters.num_field", g("hyper_parameters.sparse_inputs_slots") - 1),
                          self_interaction=False, device=device, kernels=kernels)
-
-    def create_feeds(self, batch_data, config, device="cuda"):
-        return slot_feeds(batch_data, config, device)
 
     def create_metrics(self, device="cuda"):
         """[Auc("ROC"), Accuracy()] (dygraph_model.py:58-63): the AUC bucket pair and a (correct, total) int64 pair."""

@@ -11,7 +11,7 @@ so  d = raw @ [-1, +1]^T  (rec_gemm_f32, N = 1),  rec_bce_with_logits(d, t) -> p
 """
 import torch
 
-from .deepfm import NUM_THRESHOLDS, _OnSide, auc_metrics, slot_feeds
+from .slot_net import NUM_THRESHOLDS, SlotDygraphModel, _OnSide
 from .wide_deep import SlotMLPBase
 
 
@@ -42,7 +42,7 @@ class DNNLayer(SlotMLPBase):
         k = self.k
         ids = self._concat_ids(sparse_inputs)
         B, S = ids.shape
-        t, on_gpu, cur, side, groups = self._begin_step(ids)
+        t, cur, side, groups = self._begin_step(B * S)
         x = self._features(ids, dense_inputs)
         with _OnSide(side, cur):                                   # merge keys depend on the ids only
             k.ids_group(ids, self.sparse_feature_number, None, self.ws_group, None, self.status, groups)
@@ -53,12 +53,14 @@ class DNNLayer(SlotMLPBase):
             k.auc_histogram(pred, label, auc_stats[0], auc_stats[1], NUM_THRESHOLDS)
         draw = k.gemm(dd, self._diff_t, self.ws)                                           # [B,2] = (-dd, +dd)
         dx = k.mlp_backward(draw, acts, self.mlp_w, self.mlp_dw, self.mlp_db, self.ws_mlp)
-        self._finish_step(groups, dx, S, t, lr, on_gpu, cur, side)
+        self._update_embedding(groups, dx, S, t, lr, cur, side)
+        self._finish_step(t, lr, cur, side)
         return loss, pred
 
 
-class DygraphModel:
-    """dnn/dygraph_model.py:23-98 — same method names; tensors are torch device tensors."""
+class DygraphModel(SlotDygraphModel):
+    """dnn/dygraph_model.py:23-98."""
+    print_loss = True
 
     def create_model(self, config, device="cuda", kernels=None):
         g = config.get
@@ -66,22 +68,5 @@ class DygraphModel:
                         g("hyper_parameters.dense_input_dim"), g("hyper_parameters.sparse_inputs_slots") - 1,
                         g("hyper_parameters.fc_sizes"), device=device, kernels=kernels)
 
-    def create_feeds(self, batch_data, config, device="cuda"):
-        return slot_feeds(batch_data, config, device)
-
-    def create_metrics(self, device="cuda"):
-        return auc_metrics(device)
-
-    def train_forward(self, dy_model, metrics_list, batch_data, config):
-        label, sparse, dense = self.create_feeds(batch_data, config, dy_model.device)
-        lr = config.get("hyper_parameters.optimizer.learning_rate", 0.001)
-        loss, _ = dy_model.train_step(sparse, dense, label, lr, metrics_list[0] if metrics_list else None)
-        return loss, metrics_list, {"loss": loss}
-
-    def infer_forward(self, dy_model, metrics_list, batch_data, config):
-        label, sparse, dense = self.create_feeds(batch_data, config, dy_model.device)
-        pred = dy_model.predict(dy_model.forward(sparse, dense))
-        if metrics_list:
-            dy_model.k.auc_histogram(pred.contiguous(), label.contiguous(), metrics_list[0][0], metrics_list[0][1],
-                                     NUM_THRESHOLDS)
-        return metrics_list, None
+    def predict(self, dy_model, out):
+        return dy_model.predict(out)

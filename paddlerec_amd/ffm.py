@@ -16,18 +16,17 @@ import math
 
 import torch
 
-from . import ops
-from .deepfm import NUM_THRESHOLDS, _FlatParams, _OnSide, auc_metrics, slot_feeds
+from .deepfm import _FlatParams
+from .slot_net import NUM_THRESHOLDS, SlotDygraphModel, SlotLayerBase, _OnSide, _round_up
 
 
-class FFMLayer:
+class FFMLayer(SlotLayerBase):
     """ffm/net.py:21-46.  forward(sparse_inputs, dense_inputs) -> predict [B,1]."""
     lazy_mode = False   # the dygraph default; the trainer's hyper_parameters.optimizer.lazy_mode sets it
 
     def __init__(self, sparse_feature_number, sparse_feature_dim, dense_feature_dim, sparse_num_field,
                  device="cuda", kernels=None):
-        self.device = torch.device(device)
-        self.k = kernels if kernels is not None else ops     # tests may inject a stand-in backend (host logic only)
+        self._init_runtime(device, kernels)
         self.sparse_feature_number = sparse_feature_number
         self.sparse_feature_dim = sparse_feature_dim
         self.dense_feature_dim = dense_feature_dim
@@ -37,7 +36,7 @@ class FFMLayer:
             raise ValueError("sparse_num_field %d must exceed dense_feature_dim %d" % (F, Dn))
         R = F * D
         self.row_width = R
-        self.row_pad = (R + 3) // 4 * 4
+        self.row_pad = _round_up(R, 4)
         std = 0.1 / math.sqrt(float(D))                                      # net.py:59-75 TruncatedNormal
         # (not `table`: checkpoint.py reads a `table` attribute as a PS accessor table)
         self.emb_table = torch.zeros(N, self.row_pad, dtype=torch.float32, device=self.device)
@@ -49,34 +48,13 @@ class FFMLayer:
                                  self.device)
         self.dense.p["ffm.dense_w_one"].fill_(1.0)                           # net.py:78-82 Constant(1.0)
         self.dense.p["ffm.dense_w"].fill_(1.0)                               # net.py:84-91
-        self.sparse_state = None
-        self.ws = self.k.Workspace(self.device)
         self.ws_bwd = self.k.Workspace(self.device)
-        self.ws_group = self.k.Workspace(self.device)
-        self.status = self.k.new_status(self.device)
-        self.step_count = 0
-        self._side = None
-        self._groups = None
 
     # -- parameters under the reference's state_dict keys ---------------------------------------
     def state_dict(self):
         sd = {"ffm.embedding_one.weight": self.embedding_one, "ffm.embedding.weight": self.embedding}
         sd.update(self.dense.p)
         return sd
-
-    def set_dict(self, sd):
-        for k, v in sd.items():
-            dst = self.state_dict()[k]
-            dst.copy_(torch.as_tensor(v).to(dst.device).reshape(dst.shape))
-
-    def parameters(self):
-        return list(self.state_dict().values())
-
-    @staticmethod
-    def _concat_ids(sparse_inputs):
-        if isinstance(sparse_inputs, (list, tuple)):
-            return torch.cat(list(sparse_inputs), dim=1).contiguous()        # net.py:94
-        return sparse_inputs
 
     def _fwd(self, ids, dense_inputs):
         return self.k.ffm_fwd(ids, dense_inputs, self.emb_table, self.embedding_one, self.dense.p["ffm.dense_w"],
@@ -91,29 +69,17 @@ class FFMLayer:
 
     def _ensure_sparse_state(self):
         if self.sparse_state is None:
-            N, Rp = self.emb_table.shape
-            z = lambda w: torch.zeros(N, w, dtype=torch.float32, device=self.device)
-            self.sparse_state = dict(m=z(Rp), v=z(Rp), m1=z(1), v1=z(1))
+            self.sparse_state = self._separate_moments(*self.emb_table.shape)
 
     # -- one full training step: train_forward + backward + optimizer.step ----------------------
     def train_step(self, sparse_inputs, dense_inputs, label, lr=1e-3, auc_stats=None):
         """ffm/dygraph_model.py:69-84 + tools/trainer.py:148-152.  label [B,1] int64.
         Returns (loss [1] device tensor, pred [B,1])."""
         k = self.k
-        ids = self._concat_ids(sparse_inputs)
+        ids = self._concat_ids(sparse_inputs)                      # net.py:94
         B, S = ids.shape
         D, Dn, R = self.sparse_feature_dim, self.dense_feature_dim, self.row_width
-        self._ensure_sparse_state()
-        self.step_count += 1
-        t = self.step_count
-        on_gpu = self.device.type == "cuda"
-        cur = torch.cuda.current_stream() if on_gpu else None
-        if on_gpu and self._side is None:
-            self._side = k.concurrent_stream(self.device)
-        side = self._side if on_gpu else None
-        if self._groups is None or self._groups.n != B * S:
-            self._groups = k.IdGroups(B * S, self.device)
-        groups = self._groups
+        t, cur, side, groups = self._begin_step(B * S)
         y1, y2, _ = self._fwd(ids, dense_inputs)
         with _OnSide(side, cur):                                   # merge keys depend on the ids only
             k.ids_group(ids, self.sparse_feature_number, None, self.ws_group, None, self.status, groups)
@@ -124,30 +90,18 @@ class FFMLayer:
         k.colsum(dz, self.ws, out=self.dense.g["bias"])            # d loss / d bias = sum_b dz[b]
         row_grad, _, _ = k.ffm_bwd(
             ids, dense_inputs, self.emb_table, self.dense.p["ffm.dense_w"], dz, D, self.ws_bwd,
-            out=(self._row_grad_buf(B * S), self.dense.g["ffm.dense_w"].view(Dn, R), self.dense.g["ffm.dense_w_one"]),
+            out=(self._buf("_rg", (B * S, self.row_pad)), self.dense.g["ffm.dense_w"].view(Dn, R),
+                 self.dense.g["ffm.dense_w_one"]),
             status=self.status)
         st = self.sparse_state
-        Rp = self.row_pad
-        with _OnSide(side, cur):
-            upd = k.sparse_adam_rows if self.lazy_mode else k.adam_rows_all
-            pp = self._pp = k.segment_partials(groups, row_grad, Rp, out=getattr(self, "_pp", None))
-            pp1 = self._pp1 = k.segment_partials(groups, dz, 1, grad_div=S, out=getattr(self, "_pp1", None))
-            upd(groups, row_grad, 1, self.emb_table, st["m"], st["v"], t, lr, partials=pp)
-            upd(groups, dz, S, self.embedding_one, st["m1"], st["v1"], t, lr, partials=pp1)
-        k.adam_dense(self.dense.data, self.dense.m, self.dense.v, self.dense.grad, t, lr)
-        if on_gpu:
-            cur.wait_stream(self._side)
+        self._update_rows(t, lr, cur, side, (groups, row_grad, 1, self.emb_table, st["m"], st["v"]),
+                          (groups, dz, S, self.embedding_one, st["m1"], st["v1"]))
+        self._finish_step(t, lr, cur, side)
         return loss, pred
 
-    def _row_grad_buf(self, n):
-        b = getattr(self, "_rg", None)
-        if b is None or b.shape[0] != n:
-            self._rg = torch.empty(n, self.row_pad, dtype=torch.float32, device=self.device)
-        return self._rg
 
-
-class DygraphModel:
-    """ffm/dygraph_model.py:20-99 — same method names; tensors are torch device tensors."""
+class DygraphModel(SlotDygraphModel):
+    """ffm/dygraph_model.py:20-99."""
 
     def create_model(self, config, device="cuda", kernels=None):
         dense_dim = config.get("hyper_parameters.dense_input_dim")
@@ -155,23 +109,3 @@ class DygraphModel:
                         config.get("hyper_parameters.sparse_feature_dim"), dense_dim,
                         config.get("hyper_parameters.sparse_inputs_slots") - 1 + dense_dim,   # dygraph_model.py:31-32
                         device=device, kernels=kernels)
-
-    def create_feeds(self, batch_data, config, device="cuda"):
-        return slot_feeds(batch_data, config, device)
-
-    def create_metrics(self, device="cuda"):
-        return auc_metrics(device)
-
-    def train_forward(self, dy_model, metrics_list, batch_data, config):
-        label, sparse, dense = self.create_feeds(batch_data, config, dy_model.device)
-        lr = config.get("hyper_parameters.optimizer.learning_rate", 0.001)
-        loss, _ = dy_model.train_step(sparse, dense, label, lr, metrics_list[0] if metrics_list else None)
-        return loss, metrics_list, None
-
-    def infer_forward(self, dy_model, metrics_list, batch_data, config):
-        label, sparse, dense = self.create_feeds(batch_data, config, dy_model.device)
-        pred = dy_model.forward(sparse, dense)
-        if metrics_list:
-            dy_model.k.auc_histogram(pred.contiguous(), label.contiguous(), metrics_list[0][0], metrics_list[0][1],
-                                     NUM_THRESHOLDS)
-        return metrics_list, None

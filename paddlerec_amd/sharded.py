@@ -616,13 +616,13 @@ class ShardedDeepFMLayer(DeepFMLayer):
                 h, acts = k.mlp_forward(feat.view(B, -1), mlp_w[:-1], self.mlp_b[:-1], self.ws_mlp, relu_last=True)
                 pred, dz, _, g_head = k.ctr_head(h, mlp_w[-1], self.mlp_b[-1], y1, y2, label, self.ws, mlp_dw[-1],
                                                  self.mlp_db[-1], mean_over=G * B,
-                                                 out=(self._buf("pred", (B, 1)), self._buf("dz", (B, 1)), loss_slot,
-                                                      self._buf("g_head", (B, mlp_w[-1].shape[0]))))
+                                                 out=(self._buf("_b_pred", (B, 1)), self._buf("_b_dz", (B, 1)), loss_slot,
+                                                      self._buf("_b_g_head", (B, mlp_w[-1].shape[0]))))
             else:
                 y_dnn, acts = self.k.mlp_forward(feat.view(B, -1), mlp_w, self.mlp_b, self.ws_mlp)
         if not fused_head:
             pred, dz, _ = k.sigmoid_logloss(y1, y2, y_dnn, label, self.ws, mean_over=G * B,
-                                            out=(self._buf("pred", (B, 1)), self._buf("dz", (B, 1)),
+                                            out=(self._buf("_b_pred", (B, 1)), self._buf("_b_dz", (B, 1)),
                                                  loss_slot))
         if auc_stats is not None:
             k.auc_histogram(pred, label, auc_stats[0], auc_stats[1], NUM_THRESHOLDS)
@@ -638,7 +638,7 @@ class ShardedDeepFMLayer(DeepFMLayer):
         with self._timed("fm_bwd"):
             row_grad, _, _ = k.deepfm_fm_bwd(
                 dense_inputs, feat, sum_emb, d_flat.view(B, self.fp, -1), dz, dz, S, self.ws,
-                out=(self._row_grad_buf(B * S),
+                out=(self._buf("_rg", (B * S, self.sparse_feature_dim)),
                      self.dense.g["fm.dense_w"].view(self.dense_feature_dim, -1),
                      self.dense.g["fm.dense_w_one"]),
                 dense_w=self.dense.p["fm.dense_w"], compact=self.compact)
@@ -745,10 +745,3 @@ class ShardedDeepFMLayer(DeepFMLayer):
             cap = rows + rows // 8 + 1
             b = self._xbuf[name] = torch.empty((cap, cols) if cols else (cap,), dtype=dtype, device=self.device)
         return b[:rows]
-
-    def _buf(self, name, shape):
-        b = getattr(self, "_b_" + name, None)
-        if b is None or tuple(b.shape) != tuple(shape):
-            b = torch.empty(*shape, dtype=torch.float32, device=self.device)
-            setattr(self, "_b_" + name, b)
-        return b

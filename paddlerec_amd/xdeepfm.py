@@ -21,7 +21,8 @@ import os
 
 import torch
 
-from .deepfm import NUM_THRESHOLDS, DeepFMLayer, _OnSide, _round_up, auc_metrics, slot_feeds
+from .deepfm import DeepFMLayer
+from .slot_net import NUM_THRESHOLDS, SlotDygraphModel, _OnSide, _round_up
 
 L2_COEFF = 1e-4            # net.py:139,150,219
 # bytes of the outer-product scratch (Z / Y) per batch chunk.  Small enough to stay in the 256 MB Infinity Cache between
@@ -70,7 +71,7 @@ class xDeepFMLayer(DeepFMLayer):
         self._zbuf = None
         self._keep_bufs, self._kept = {}, {}
         self._bias_sum = torch.zeros(1, dtype=torch.float32, device=self.device)
-        self._zeros = None
+        self._groups = None
 
     def state_dict(self):
         sd = super().state_dict()
@@ -264,16 +265,7 @@ class xDeepFMLayer(DeepFMLayer):
         ids = self._concat_ids(sparse_inputs)
         B, S = ids.shape
         D, Dn = self.sparse_feature_dim, self.dense_feature_dim
-        self._ensure_sparse_state()
-        self.step_count += 1
-        on_gpu = self.device.type == "cuda"
-        cur = torch.cuda.current_stream() if on_gpu else None
-        if on_gpu and self._side is None:
-            self._side = k.concurrent_stream(self.device)
-        side = self._side if on_gpu else None
-        groups = getattr(self, "_groups", None)
-        if groups is None or groups.n != B * S:
-            groups = self._groups = k.IdGroups(B * S, self.device)
+        t, cur, side, groups = self._begin_step(B * S)
         sv = {}
         y1, y_cin, y_dnn = self._logit_parts(ids, dense_inputs, keep=sv)
         with _OnSide(side, cur):                                   # merge keys depend on the ids only
@@ -289,15 +281,14 @@ class xDeepFMLayer(DeepFMLayer):
         d_flat = k.mlp_backward(dz, sv["acts"], self.mlp_w, self.mlp_dw, self.mlp_db, self.ws_mlp)   # [B, F*D]
         dfeat = d_flat.view(B, self.num_field, D)
         self._cin_backward(sv["feat"], sv["xts"], dpooled, dfeat)
-        if self._zeros is None or self._zeros.shape[0] != B:
-            self._zeros = torch.zeros(B, 1, dtype=torch.float32, device=self.device)
-        row_grad, _, _ = k.deepfm_fm_bwd(dense_inputs, sv["feat"], sv["sum_emb"], dfeat, dz, self._zeros, S, self.ws,
-                                         out=(self._row_grad_buf(B * S), g["fm.dense_w"].view(Dn, -1),
+        zeros = self._buf("_zeros", (B, 1), zero=True)
+        row_grad, _, _ = k.deepfm_fm_bwd(dense_inputs, sv["feat"], sv["sum_emb"], dfeat, dz, zeros, S, self.ws,
+                                         out=(self._buf("_rg", (B * S, D)), g["fm.dense_w"].view(Dn, -1),
                                               g["fm.dense_w_one"]),
                                          dense_w=p["fm.dense_w"], compact=False)
         for name in self._decayed:                                  # L2Decay: grad += coeff * w
             k.sgd_dense(g[name], p[name], -L2_COEFF)
-        t, st = self.step_count, self.sparse_state
+        st = self.sparse_state
         with _OnSide(side, cur):
             pp = self._pp = k.segment_partials(groups, row_grad, D, out=getattr(self, "_pp", None))
             pp1 = self._pp1 = k.segment_partials(groups, dz, 1, grad_div=S, out=getattr(self, "_pp1", None))
@@ -305,14 +296,12 @@ class xDeepFMLayer(DeepFMLayer):
                                  v_offset=_round_up(D, 4), partials=pp, partials1=pp1)
         if allreduce is not None:
             allreduce(self.dense.grad)
-        k.adam_dense(self.dense.data, self.dense.m, self.dense.v, self.dense.grad, t, lr)
-        if side is not None:
-            cur.wait_stream(self._side)
+        self._finish_step(t, lr, cur, side)
         return loss, pred
 
 
-class DygraphModel:
-    """xdeepfm/dygraph_model.py:23-104 — same method names; tensors are torch device tensors."""
+class DygraphModel(SlotDygraphModel):
+    """xdeepfm/dygraph_model.py:23-104."""
 
     def create_model(self, config, device="cuda", kernels=None):
         g = config.get
@@ -320,23 +309,3 @@ class DygraphModel:
                             g("hyper_parameters.dense_input_dim"), g("hyper_parameters.sparse_inputs_slots") - 1,
                             g("hyper_parameters.layer_sizes_cin"), g("hyper_parameters.layer_sizes_dnn"),
                             device=device, kernels=kernels)
-
-    def create_feeds(self, batch_data, config, device="cuda"):
-        return slot_feeds(batch_data, config, device)
-
-    def create_metrics(self, device="cuda"):
-        return auc_metrics(device)
-
-    def train_forward(self, dy_model, metrics_list, batch_data, config):
-        label, sparse, dense = self.create_feeds(batch_data, config, dy_model.device)
-        lr = config.get("hyper_parameters.optimizer.learning_rate", 0.001)
-        loss, _ = dy_model.train_step(sparse, dense, label, lr, metrics_list[0] if metrics_list else None)
-        return loss, metrics_list, None
-
-    def infer_forward(self, dy_model, metrics_list, batch_data, config):
-        label, sparse, dense = self.create_feeds(batch_data, config, dy_model.device)
-        pred = dy_model.forward(sparse, dense)
-        if metrics_list:
-            dy_model.k.auc_histogram(pred.contiguous(), label.contiguous(), metrics_list[0][0], metrics_list[0][1],
-                                     NUM_THRESHOLDS)
-        return metrics_list, None
