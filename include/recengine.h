@@ -831,6 +831,38 @@ int rec_gemm_f32_pair(const rec_gemm_desc* desc0, const float* A0, const float* 
                       const rec_gemm_epilogue_args* args0 /* may be NULL */, const rec_gemm_desc* desc1, const float* A1,
                       const float* B1, float* C1, const rec_gemm_epilogue_args* args1 /* may be NULL */, void* workspace,
                       size_t workspace_bytes, void* stream);
+/* Which kernel the calling thread's last rec_gemm_f32 / rec_gemm_f32_pair call launched (host bookkeeping: one struct
+ * store per call, nothing on the device).  The routing rules depend on shapes, alignment and process environment; a
+ * test that means one kernel asserts it here instead of trusting its shape.  A call refused before its launch leaves
+ * the previous report; before the thread's first call family is -1. */
+typedef enum {
+  REC_GEMM_ROUTE_SKINNY_ROWS = 0, /* N <= 4: one wave per row */
+  REC_GEMM_ROUTE_SKINNY_DW = 1,   /* N <= 4, trans_a, long K: k-chunk partials + the split-K reduce */
+  REC_GEMM_ROUTE_X3_DW = 2,       /* bf16 x 3 weight gradient + the split-K reduce */
+  REC_GEMM_ROUTE_X3 = 3,          /* bf16 x 3 forward / dX */
+  REC_GEMM_ROUTE_PANEL = 4,       /* row-panel kernel */
+  REC_GEMM_ROUTE_GLDS = 5,        /* LDS-DMA ring */
+  REC_GEMM_ROUTE_DIRECT = 6,      /* one launch, a wave per 16 x 16 tile */
+  REC_GEMM_ROUTE_TILED = 7        /* register-staged tiles (+ the split-K reduce when splits > 1) */
+} rec_gemm_route_family;
+enum {
+  REC_GEMM_ROUTE_FAST = 1,        /* tiled: branch-free tile loaders (aligned operands, extents multiples of 4) */
+  REC_GEMM_ROUTE_PIPE = 2,        /* tiled: the whole-tile pipe kernel */
+  REC_GEMM_ROUTE_VEC = 4,         /* direct: float4 loads along k */
+  REC_GEMM_ROUTE_KS4 = 8,         /* direct: K split over the workgroup's four waves */
+  REC_GEMM_ROUTE_FOLD = 16,       /* tiled split-K: K slices folded into a 1-D grid */
+  REC_GEMM_ROUTE_VEC_A = 32,      /* skinny rows: float4 loads of A */
+  REC_GEMM_ROUTE_PAIR = 64        /* direct: both GEMMs of rec_gemm_f32_pair in one launch (VEC / KS4: of desc1) */
+};
+typedef struct {
+  int32_t family; /* rec_gemm_route_family */
+  int32_t cfg;    /* tiled: index of the tile config launched (0 128x80, 1 256x80, 2 256x128, 3 128x128, 4 80x80,
+                     5 64x80, 6 128x80 at 4 blocks/CU, 7 144x80); else -1 */
+  int32_t splits; /* tiled, skinny_dw, x3_dw: K slices; 1 = the GEMM kernel applied the epilogue itself, > 1 = the
+                     reduce kernel did.  Every other family: 1 */
+  int32_t flags;  /* REC_GEMM_ROUTE_* bits */
+} rec_gemm_route;
+int rec_gemm_last_route(rec_gemm_route* out);
 /* Weight images ahead of time.  Under the bf16 x 3 family every forward / dX call splits op(B) [k, n] into its plane image
  * first (a ~5 us launch per call); the weights of a tower change once per step, so a trainer makes ALL images of the step
  * in one launch right after its optimizer (rec_adam_dense) and passes them as rec_gemm_epilogue_args.b_image.

@@ -177,6 +177,16 @@ class GemmEpilogueArgs(C.Structure):
                 ("b_colsum", C.c_void_p), ("b_image", C.c_void_p), ("relu_bits", C.c_void_p)]
 
 
+class GemmRoute(C.Structure):
+    """rec_gemm_route (include/recengine.h)."""
+    _fields_ = [("family", C.c_int32), ("cfg", C.c_int32), ("splits", C.c_int32), ("flags", C.c_int32)]
+
+
+GEMM_ROUTE_FAMILIES = ("skinny_rows", "skinny_dw", "x3_dw", "x3", "panel", "glds", "direct", "tiled")
+GEMM_ROUTE_FLAGS = dict(fast=1, pipe=2, vec=4, ks4=8, fold=16, vec_a=32, pair=64)
+GEMM_CFGS = ("128x80", "256x80", "256x128", "128x128", "80x80", "64x80", "128x80_o4", "144x80")
+
+
 class GemmBImage(C.Structure):
     _fields_ = [("B", C.c_void_p), ("ldb", C.c_int32), ("k", C.c_int32), ("n", C.c_int32), ("trans_b", C.c_int32),
                 ("image", C.c_void_p)]
@@ -313,6 +323,7 @@ SIGNATURES = {
     "rec_shard_route_workspace_bytes": (C.c_int, [_I64, _I32, C.POINTER(_SZ)]),
     "rec_shard_route": (C.c_int, [_I64, _I32, _I64, _I64, _I32] + [_P] * 9 + [_SZ, _P]),
     "rec_gemm_f32_workspace_bytes": (C.c_int, [C.POINTER(GemmDesc), C.POINTER(_SZ)]),
+    "rec_gemm_last_route": (C.c_int, [C.POINTER(GemmRoute)]),
     "rec_gemm_plan_splits": (C.c_int, [C.POINTER(GemmDesc), _I32, C.POINTER(_I32)]),
     "rec_gemm_relu_bits_bytes": (C.c_int, [C.POINTER(GemmDesc), C.POINTER(_I32), C.POINTER(_SZ)]),
     "rec_gemm_b_image_bytes": (C.c_int, [_I32, _I32, C.POINTER(_I32), C.POINTER(_SZ)]),

@@ -242,6 +242,7 @@ inline void launch_direct_epi(const rec_gemm_desc* d, const float* A, const floa
   const bool vec = direct_vec(d, A, B), split = direct_split(d);
   unsigned grid = 0;
   const DirectArgs w = direct_args(d, A, B, C, e, colsum_out, split, &grid);
+  set_route(REC_GEMM_ROUTE_DIRECT, -1, 1, (vec ? REC_GEMM_ROUTE_VEC : 0) | (split ? REC_GEMM_ROUTE_KS4 : 0));
 #define REC_DIRECT_LAUNCH(VEC_, KS_) \
   hipLaunchKernelGGL((gemm_f32_direct_kernel<TA, TB, EPI, VEC_, KS_>), dim3(grid), dim3(256), 0, st, w)
   if (split) {
@@ -293,6 +294,7 @@ inline bool launch_direct_pair(const rec_gemm_desc* d0, const float* A0, const f
   const DirectArgs w0 = direct_args(d0, A0, B0, C0, e0, colsum0, s0, &g0);
   const DirectArgs w1 = direct_args(d1, A1, B1, C1, e1, nullptr, s1, &g1);
   if ((uint64_t)g0 + g1 >= (1ull << 31)) return false;
+  set_route(REC_GEMM_ROUTE_DIRECT, -1, 1, REC_GEMM_ROUTE_PAIR | REC_GEMM_ROUTE_VEC | (s1 ? REC_GEMM_ROUTE_KS4 : 0));
 #define REC_PAIR_LAUNCH(E_, K0_, K1_) \
   hipLaunchKernelGGL((gemm_f32_direct_pair_kernel<E_, K0_, K1_>), dim3(g0 + g1), dim3(256), 0, st, w0, w1, g0)
 #define REC_PAIR_KS(E_)                                        \

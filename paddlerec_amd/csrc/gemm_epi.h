@@ -10,6 +10,12 @@ typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
 constexpr int kBK = 16;
 
+// the kernel this thread's last GEMM call launched (rec_gemm_last_route): written on the host where the choice is made
+inline thread_local rec_gemm_route g_gemm_route = {-1, -1, 0, 0};
+inline void set_route(int family, int cfg = -1, int splits = 1, int flags = 0) {
+  g_gemm_route = rec_gemm_route{family, cfg, splits, flags};
+}
+
 // ---------------------------------------------------------------------------------- tile loader
 // Logical tile T[R][C] of a matrix; MEMT: memory is contiguous along R (element (r,c) at p[c*ld + r]).
 // load(): the thread's float4s of the tile (zeros outside [rmax, cmax)); vec_ok = 16-B aligned rows.

@@ -709,9 +709,12 @@ static void launch_one(const rec_gemm_desc* d, const GemmPlan& p, const float* A
       hipLaunchKernelGGL((gemm_f32_pipe_kernel<BM, BN, WM_, WN_, OCC, TA, TB, EPI>), grid, dim3(WM_ * WN_ * kWave), shmem,
                          st, d->m, d->n, d->k, A, (int64_t)d->lda, B, (int64_t)d->ldb, C, (int64_t)d->ldc, e, p.tiles_n,
                          p.tiles_total, p.k_chunk, partial, cpart, fold ? p.splits : 1);
+      set_route(REC_GEMM_ROUTE_TILED, p.cfg, p.splits,
+                REC_GEMM_ROUTE_FAST | REC_GEMM_ROUTE_PIPE | (fold ? REC_GEMM_ROUTE_FOLD : 0));
       return;
     }
   }
+  set_route(REC_GEMM_ROUTE_TILED, p.cfg, p.splits, (fast ? REC_GEMM_ROUTE_FAST : 0) | (fold ? REC_GEMM_ROUTE_FOLD : 0));
   hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, WM_, WN_, OCC, TA, TB, EPI>), grid, dim3(WM_ * WN_ * kWave),
                      shmem, st, d->m, d->n, d->k, A, (int64_t)d->lda, B, (int64_t)d->ldb, C,
                      (int64_t)d->ldc, e, p.tiles_n, p.tiles_total, p.k_chunk, vec_a, vec_b, fast, partial, cpart,
@@ -900,6 +903,7 @@ static bool launch_x3_dw(const rec_gemm_desc* d, const float* A, const float* B,
   GemmPlan sp{};
   sp.splits = pl.slices;
   launch_reduce<REC_EPI_NONE>(d, sp, partial, C, e, st, b_colsum ? cpart : nullptr, b_colsum);
+  set_route(REC_GEMM_ROUTE_X3_DW, -1, pl.slices);
   return true;
 }
 
@@ -984,6 +988,12 @@ extern "C" int rec_gemm_b_images(int32_t count, const rec_gemm_b_image* items, v
     hipLaunchKernelGGL(x3_split_batch_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, b);
     if (int rc = check_launch("rec_gemm_b_images")) return rc;
   }
+  return REC_OK;
+}
+
+extern "C" int rec_gemm_last_route(rec_gemm_route* out) {
+  REC_REQUIRE(out, REC_EINVAL, "out is NULL");
+  *out = g_gemm_route;
   return REC_OK;
 }
 
@@ -1082,6 +1092,7 @@ extern "C" int rec_gemm_f32(const rec_gemm_desc* desc, const float* A, const flo
       REC_GEMV_CASE(REC_EPI_DSIGMOID) REC_GEMV_CASE(REC_EPI_DTANH)
     }
 #undef REC_GEMV_CASE
+    set_route(REC_GEMM_ROUTE_SKINNY_ROWS, -1, 1, vec_a ? REC_GEMM_ROUTE_VEC_A : 0);
     return check_launch("rec_gemm_f32 (skinny rows)");
   }
   if (skinny_dw(desc) && epi == REC_EPI_NONE) {
@@ -1099,16 +1110,25 @@ extern "C" int rec_gemm_f32(const rec_gemm_desc* desc, const float* A, const flo
     if (b_colsum)
       hipLaunchKernelGGL(colsum_reduce_kernel, dim3((desc->n + kBlock - 1) / kBlock), dim3(kBlock), 0, st,
                          desc->n, z, (const float*)cpart2, b_colsum);
+    set_route(REC_GEMM_ROUTE_SKINNY_DW, -1, z);
     return check_launch("rec_gemm_f32 (skinny dW)");
   }
   if (launch_x3_dw(desc, A, B, C, e, b_colsum, workspace, workspace_bytes, st)) return check_launch("rec_gemm_f32 (bf16x3 dW)");
   // tall problems of the towers' own widths: whole row panels, one resident round (gemm_panel.h)
-  if (!b_colsum && launch_x3(desc, A, B, C, e, x->b_image, workspace, workspace_bytes, st))
+  if (!b_colsum && launch_x3(desc, A, B, C, e, x->b_image, workspace, workspace_bytes, st)) {
+    set_route(REC_GEMM_ROUTE_X3);
     return check_launch("rec_gemm_f32 (bf16x3)");
+  }
   // (no other kernel knows the bit mask: a call that asked for it never continues on one that would ignore it)
   REC_REQUIRE(!relu_bits, REC_EINVAL, "relu_bits: the call did not take the bf16 x 3 kernel (alignment / workspace)");
-  if (!b_colsum && launch_panel(desc, A, B, C, e, st, device_cus())) return check_launch("rec_gemm_f32 (panel)");
-  if (!b_colsum && launch_glds(desc, A, B, C, e, st)) return check_launch("rec_gemm_f32 (glds)");
+  if (!b_colsum && launch_panel(desc, A, B, C, e, st, device_cus())) {
+    set_route(REC_GEMM_ROUTE_PANEL);
+    return check_launch("rec_gemm_f32 (panel)");
+  }
+  if (!b_colsum && launch_glds(desc, A, B, C, e, st)) {
+    set_route(REC_GEMM_ROUTE_GLDS);
+    return check_launch("rec_gemm_f32 (glds)");
+  }
   // the launch-bound sizes (the reference's own batches): one launch, a wave per 16 x 16 tile over the whole K (gemm_direct.h)
   if (launch_direct(desc, A, B, C, e, b_colsum, st)) return check_launch("rec_gemm_f32 (direct)");
   const GemmPlan p = plan_gemm(desc);

@@ -4,6 +4,7 @@ torch is plumbing here (device memory, streams); every op below is a hand-writte
 librecengine.so.  Tensors must live on a ROCm device — there is deliberately no CPU path.
 Reference call sites are cited in include/recengine.h next to each entry point.
 """
+import collections
 import ctypes as C
 import os
 
@@ -1876,6 +1877,21 @@ def linear_backward(X, G, W, ws, dW, db, relu_src=None, b_image=None, epilogue=N
     check(lib().rec_gemm_f32_pair(C.byref(d0), _p(X), _p(G), _p(dW), C.byref(x0), C.byref(d1), _p(G), _p(W), _p(dX),
                                   C.byref(x1), _p(w), C.c_size_t(w.numel()), _stream()), "rec_gemm_f32_pair")
     return dX
+
+
+GemmRouteInfo = collections.namedtuple("GemmRouteInfo", "family cfg splits flags")
+
+
+def gemm_last_route():
+    """Which kernel this thread's last gemm() / linear_backward() call launched (rec_gemm_last_route): family as a
+    string (_lib.GEMM_ROUTE_FAMILIES; None before the first call), cfg = the tiled kernels' tile config ("128x80", ...;
+    None elsewhere), splits = K slices (> 1: the split-K reduce applied the epilogue), flags = the names of the set
+    _lib.GEMM_ROUTE_FLAGS bits as a frozenset."""
+    r = _lib.GemmRoute()
+    check(lib().rec_gemm_last_route(C.byref(r)), "rec_gemm_last_route")
+    return GemmRouteInfo(_lib.GEMM_ROUTE_FAMILIES[r.family] if r.family >= 0 else None,
+                         _lib.GEMM_CFGS[r.cfg] if r.cfg >= 0 else None, r.splits,
+                         frozenset(n for n, b in _lib.GEMM_ROUTE_FLAGS.items() if r.flags & b))
 
 
 _relu_bits_cache = {}

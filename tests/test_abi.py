@@ -77,6 +77,31 @@ def test_host_planning_queries(engine_lib):
     assert engine_lib.rec_segment_partials_bytes(-1, 16, C.byref(n)) == -1
 
 
+def test_gemm_route_report_without_gpu(engine_lib):
+    """rec_gemm_last_route is host bookkeeping: it answers on a GPU-less host, and a call that is refused before it
+    chooses a kernel leaves the report as it was."""
+    import ctypes as C
+    from paddlerec_amd import _lib
+    L = engine_lib
+    assert L.rec_gemm_last_route(None) == -1
+    r0, r1 = _lib.GemmRoute(), _lib.GemmRoute()
+    assert L.rec_gemm_last_route(C.byref(r0)) == 0
+    assert -1 <= r0.family < len(_lib.GEMM_ROUTE_FAMILIES) and -1 <= r0.cfg < len(_lib.GEMM_CFGS)
+    d = _lib.GemmDesc(4, 4, 4, 4, 4, 4, 0, 0, 99, 0)                      # unknown epilogue: refused
+    assert L.rec_gemm_f32(C.byref(d), None, None, None, None, None, 0, None) == -1
+    assert L.rec_gemm_last_route(C.byref(r1)) == 0
+    assert (r1.family, r1.cfg, r1.splits, r1.flags) == (r0.family, r0.cfg, r0.splits, r0.flags)
+    # the Python names are the header's enumerators
+    src = open(os.path.join(REPO, "include", "recengine.h")).read()
+    enums = {n.lower(): int(v) for n, v in re.findall(r"\bREC_GEMM_ROUTE_([A-Z0-9_]+) = (\d+)", src)}
+    assert enums == dict({n: i for i, n in enumerate(_lib.GEMM_ROUTE_FAMILIES)}, **_lib.GEMM_ROUTE_FLAGS)
+    # ... and the tile config names are the planner's, in its order
+    hip = open(os.path.join(REPO, "paddlerec_amd", "csrc", "gemm_f32.hip")).read()
+    cfgs = re.search(r"enum GemmCfg \{([^}]*)\}", hip).group(1)
+    names = [c.split("=")[0].strip()[4:].lower() for c in cfgs.split(",") if c.strip() and "COUNT" not in c]
+    assert tuple(names) == _lib.GEMM_CFGS
+
+
 def test_more_argument_validation_without_gpu(engine_lib):
     """Every entry point rejects null pointers / bad sizes before it touches the device."""
     import ctypes as C

@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+import gemm_ref
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
@@ -24,6 +26,14 @@ def _mk(rng, *shape):
 def _check(C, want, bound):
     err = np.abs(C.astype(np.float64) - want)
     assert np.all(err <= bound + 1e-30), "max err %.3e, bound %.3e" % (err.max(), bound.max())
+
+
+def _took(ops, family, **fields):
+    """The kernel family (and, by keyword, cfg / splits) of the last ops.gemm call: a test that means one kernel says so
+    (tests/test_gemm_routes_gpu.py holds the matrix of routes x epilogues)."""
+    r = ops.gemm_last_route()
+    assert r.family == family and all(getattr(r, k) == v for k, v in fields.items()), (r, family, fields)
+    return r
 
 
 @pytest.mark.parametrize("M,N,K,ta,tb", [
@@ -62,6 +72,8 @@ def test_gemm_split_k(ops, split):
 
 
 def test_gemm_epilogues(ops):
+    # 300 x 400 x 200 is launch-bound (M N K < 1.5e8, K <= 1024): seven epilogues of the DIRECT kernel (gemm_direct.h), and
+    # bias_relu behind the split-K reduce of the tiled kernels
     rng = np.random.default_rng(3)
     M, N, K = 300, 400, 200
     A, B, bias = _mk(rng, M, K), _mk(rng, K, N) * 0.1, _mk(rng, N)
@@ -72,23 +84,31 @@ def test_gemm_epilogues(ops):
     tol = dict(rtol=1e-5, atol=1e-5)
     np.testing.assert_allclose(ops.gemm(t(A), t(B), ws, epilogue="bias", bias=t(bias)).cpu().numpy(),
                                acc + bias, **tol)
+    _took(ops, "direct")
     np.testing.assert_allclose(ops.gemm(t(A), t(B), ws, epilogue="bias_relu", bias=t(bias)).cpu().numpy(),
                                np.maximum(acc + bias, 0), **tol)
+    _took(ops, "direct")
     np.testing.assert_allclose(ops.gemm(t(A), t(B), ws, epilogue="relu_mask", aux0=t(X0)).cpu().numpy(),
                                np.where(X0 > 0, acc, 0), **tol)
+    _took(ops, "direct")
     np.testing.assert_allclose(                                   # dcn_v2/net.py:225
         ops.gemm(t(A), t(B), ws, epilogue="cross", bias=t(bias), aux0=t(X0), aux1=t(Xl)).cpu().numpy(),
         Xl + X0 * (acc + bias), **tol)
+    _took(ops, "direct")
     np.testing.assert_allclose(ops.gemm(t(A), t(B), ws, epilogue="bias_sigmoid", bias=t(bias)).cpu().numpy(),
                                1 / (1 + np.exp(-(acc + bias))), **tol)
+    _took(ops, "direct")
     np.testing.assert_allclose(ops.gemm(t(A), t(B), ws, epilogue="bias_tanh", bias=t(bias)).cpu().numpy(),
                                np.tanh(acc + bias), **tol)
+    _took(ops, "direct")
     np.testing.assert_allclose(ops.gemm(t(A), t(B), ws, epilogue="add", aux1=t(Xl)).cpu().numpy(),
                                acc + Xl, **tol)
+    _took(ops, "direct")
     # epilogue after a split-K reduction
     np.testing.assert_allclose(
         ops.gemm(t(A), t(B), ws, epilogue="bias_relu", bias=t(bias), split_k=4).cpu().numpy(),
         np.maximum(acc + bias, 0), **tol)
+    _took(ops, "tiled", splits=4)
 
 
 @pytest.mark.parametrize("M,N,K,ta,tb", [
@@ -109,6 +129,7 @@ def test_gemm_direct_kernel(ops, M, N, K, ta, tb):
     if ta and not tb:
         kw["b_colsum"] = torch.empty(N, device=DEV)
     C = ops.gemm(At, Bt, ws, trans_a=ta, trans_b=tb, **kw).cpu().numpy()
+    _took(ops, "direct")
     want = A.astype(np.float64) @ B.astype(np.float64)
     bound = 4e-7 * (np.abs(A).astype(np.float64) @ np.abs(B).astype(np.float64))
     _check(C, want, bound)
@@ -118,12 +139,14 @@ def test_gemm_direct_kernel(ops, M, N, K, ta, tb):
     assert np.array_equal(C, ops.gemm(At, Bt, ws, trans_a=ta, trans_b=tb, **kw).cpu().numpy())
     # an explicit K split takes the tiled kernels + the reduce launch: same result to the bound of both
     C2 = ops.gemm(At, Bt, ws, trans_a=ta, trans_b=tb, split_k=2).cpu().numpy()
+    _took(ops, "tiled", splits=2)
     _check(C2, want, bound)
     # strided operands (a column slice of a wider buffer): the float4 path must not be taken on unaligned rows
     if not ta and not tb and K % 4 == 0 and M > 1:
         wide = torch.zeros(M, K + 3, device=DEV)
         wide[:, 1:K + 1] = At
         C3 = ops.gemm(wide[:, 1:K + 1], Bt, ws).cpu().numpy()
+        assert "vec" not in _took(ops, "direct").flags
         assert np.array_equal(C3, C)
 
 
@@ -142,6 +165,11 @@ def test_linear_backward_pair(ops, B, nin, nout, epi):
     dW, db = torch.empty(nin, nout, device=DEV), torch.empty(nout, device=DEV)
     aux = Xt if epi != "none" else None
     dX = ops.linear_backward(Xt, Gt, Wt, ws, dW, db, epilogue=epi, aux0=aux)
+    # the launch-bound pairs with float4-loadable rows of W go out as ONE launch of the direct kernel; the others report
+    # the route of their second rec_gemm_f32 call (dX)
+    r = ops.gemm_last_route()
+    assert ("pair" in r.flags) == (B <= 512 and nin <= 432 and nout % 4 == 0), r
+    assert r.family == ("tiled" if nin == 1560 else "direct"), r
     dW2, db2 = torch.empty_like(dW), torch.empty_like(db)
     ops.gemm(Xt, Gt, ws, trans_a=True, out=dW2, b_colsum=db2)
     dX2 = ops.gemm(Gt, Wt, ws, trans_b=True, epilogue=epi, **(dict(aux0=aux) if aux is not None else {}))
@@ -166,13 +194,17 @@ def test_gemm_skinny_paths(ops):
     acc = A.astype(np.float64) @ w.astype(np.float64)
     tol = dict(rtol=1e-5, atol=1e-5)
     np.testing.assert_allclose(ops.gemm(t(A), t(w), ws, epilogue="bias", bias=t(b)).cpu().numpy(), acc + b, **tol)
+    _took(ops, "skinny_rows")
     np.testing.assert_allclose(ops.gemm(t(A), t(w), ws, epilogue="add", bias=t(b), aux1=t(item_b)).cpu().numpy(),
                                acc + b + item_b, **tol)
+    _took(ops, "skinny_rows")
     np.testing.assert_allclose(ops.gemm(t(A), t(w), ws, epilogue="bias_sigmoid", bias=t(b)).cpu().numpy(),
                                1 / (1 + np.exp(-(acc + b))), **tol)
+    _took(ops, "skinny_rows")
     G = _mk(rng, M, 1)
     db = torch.empty(1, device=DEV)
     dW = ops.gemm(t(A), t(G), ws, trans_a=True, b_colsum=db)
+    assert _took(ops, "skinny_dw").splits == (M + 127) // 128        # 128 k rows per block, folded by the split-K reduce
     np.testing.assert_allclose(dW.cpu().numpy(), A.astype(np.float64).T @ G.astype(np.float64), rtol=1e-5, atol=1e-4)
     np.testing.assert_allclose(db.cpu().numpy(), G.astype(np.float64).sum(0), rtol=1e-5, atol=1e-4)
     dW2 = ops.gemm(t(A), t(G), ws, trans_a=True, b_colsum=db)
@@ -182,6 +214,7 @@ def test_gemm_skinny_paths(ops):
         A2, G2 = _mk(rng, Kn, Mn), _mk(rng, Kn, Nn)
         db2 = torch.empty(Nn, device=DEV)
         got = ops.gemm(t(A2), t(G2), ws, trans_a=True, b_colsum=db2)
+        _took(ops, "skinny_dw")
         np.testing.assert_allclose(got.cpu().numpy(), A2.astype(np.float64).T @ G2.astype(np.float64), rtol=1e-5, atol=1e-4)
         np.testing.assert_allclose(db2.cpu().numpy(), G2.astype(np.float64).sum(0), rtol=1e-5, atol=1e-4)
         assert torch.equal(got, ops.gemm(t(A2), t(G2), ws, trans_a=True, b_colsum=db2))
@@ -234,6 +267,41 @@ def test_gemm_argument_errors(ops):
         ops.gemm(a, torch.zeros(5, 3, device=DEV), ws, epilogue="bias")
     with pytest.raises(Exception, match="device tensor"):
         ops.gemm(torch.zeros(4, 5), torch.zeros(5, 3), ws)
+    # every epilogue without one of the operands it needs, and every epilogue leading dimension below N: refused on the
+    # host, before any launch
+    from paddlerec_amd._lib import RecError
+    import ctypes as C
+    M, N = 4, 3
+    b = torch.zeros(5, N, device=DEV)
+    full = dict(bias=torch.zeros(N, device=DEV), aux0=torch.zeros(M, N, device=DEV), aux1=torch.zeros(M, N, device=DEV),
+                row_scale=torch.zeros(M, device=DEV))
+    needs = dict(bias=("bias",), bias_relu=("bias",), bias_sigmoid=("bias",), relu_mask=("aux0",), dsigmoid=("aux0",),
+                 dtanh=("aux0",), add=("aux1",), cross=("bias", "aux0", "aux1"), moe=("bias", "aux0", "aux1", "row_scale"))
+    for epi, names in needs.items():
+        ops.gemm(a, b, ws, epilogue=epi, **{n: full[n] for n in names})          # complete: accepted
+        for missing in names:
+            with pytest.raises(RecError, match="row_scale" if missing == "row_scale" else missing):
+                ops.gemm(a, b, ws, epilogue=epi, **{n: full[n] for n in names if n != missing})
+
+    def raw(epi, out2=None, **lds):
+        d, x, out, need = ops._gemm_prepare(a, b, False, False, epi, full["bias"], full["aux0"], full["aux1"], None, 0, None,
+                                            full["row_scale"], out2, 0, None)
+        for k, v in lds.items():
+            setattr(x, k, v)
+        w = ws.get(need)
+        ops.check(ops.lib().rec_gemm_f32(C.byref(d), ops._p(a), ops._p(b), ops._p(out), C.byref(x), ops._p(w),
+                                         C.c_size_t(w.numel()), ops._stream()), "rec_gemm_f32")
+    raw("moe")
+    for epi in ("relu_mask", "cross", "moe", "dsigmoid", "dtanh", "add"):
+        with pytest.raises(RecError, match="aux0"):
+            raw(epi, ld_aux0=N - 1)
+    for epi in ("cross", "add", "moe"):
+        with pytest.raises(RecError, match="aux1"):
+            raw(epi, ld_aux1=N - 1)
+    u = torch.zeros(M, N, device=DEV)
+    raw("cross", out2=u)
+    with pytest.raises(RecError, match="ld_out2"):
+        raw("cross", out2=u, ld_out2=N - 1)
 
 
 def test_stream_helpers(ops):
@@ -286,6 +354,9 @@ def test_gemm_glds_kernel(ops, M, N, K, tb, monkeypatch):
     shapes (256x80, 128x208), K from 2 to 63 tiles (ring wrap-around, 1-2 tile tails), the four epilogues — against
     float64, and bit-identical across two launches and against REC_GEMM_GLDS=0 up to the fp32 bound."""
     monkeypatch.setenv("REC_GEMM_GLDS_80", "1")       # the 256x80 configuration too (off by default: no faster)
+    # the bf16 x 3 kernel is asked first and takes every shape here with K >= 64 and N >= 336: off (read per call), or this
+    # test checks that kernel instead of the ring — the route is asserted after every call
+    monkeypatch.setenv("REC_GEMM_BF16X3", "0")
     rng = np.random.default_rng(M + N * 3 + K)
     A, B = _mk(rng, M, K), _mk(rng, K, N)
     bias, X0 = _mk(rng, N), _mk(rng, M, N)
@@ -295,27 +366,33 @@ def test_gemm_glds_kernel(ops, M, N, K, tb, monkeypatch):
     want = A.astype(np.float64) @ B.astype(np.float64)
     bound = 4e-7 * (np.abs(A).astype(np.float64) @ np.abs(B).astype(np.float64))
     C = ops.gemm(At, Bt, ws, trans_b=tb).cpu().numpy()
+    _took(ops, "glds")
     _check(C, want, bound)
     assert np.array_equal(C, ops.gemm(At, Bt, ws, trans_b=tb).cpu().numpy())
     Cb = ops.gemm(At, Bt, ws, trans_b=tb, epilogue="bias", bias=t(bias)).cpu().numpy()
+    _took(ops, "glds")
     _check(Cb, want + bias, bound + 1e-6)
     Cr = ops.gemm(At, Bt, ws, trans_b=tb, epilogue="bias_relu", bias=t(bias)).cpu().numpy()
+    _took(ops, "glds")
     _check(Cr, np.maximum(want + bias, 0), bound + 1e-6)
     Cm = ops.gemm(At, Bt, ws, trans_b=tb, epilogue="relu_mask", aux0=t(X0)).cpu().numpy()
+    _took(ops, "glds")
     _check(Cm, np.where(X0 > 0, want, 0), bound)
     # strided views (row strides larger than the logical width) take the same kernel
     wide = torch.zeros(M, K + 16, device=DEV)
     wide[:, :K] = At
     _check(ops.gemm(wide[:, :K], Bt, ws, trans_b=tb).cpu().numpy(), want, bound)
+    _took(ops, "glds")
 
 
 @pytest.mark.parametrize("M,N,K,tb", [(32768, 400, 400, False), (32768, 400, 432, False), (32768, 400, 400, True),
-                                      (32768, 432, 400, True), (65536 + 64 * 40, 400, 48, False)])
+                                      (32768, 432, 400, True), (64 * 900, 400, 48, False)])
 def test_gemm_panel_kernel(ops, M, N, K, tb, monkeypatch):
     """The row-panel kernel (csrc/gemm_panel.h: a block owns 64 rows x ALL N columns, persistent over panels, permuted
     accumulator columns, float4 epilogue) is an opt-in experiment (REC_GEMM_PANEL=1; no faster on random data, see
     profiles/r04_gemm_power.txt): against float64 and BIT-IDENTICAL to the tiled kernels (same order of additions), the
-    four epilogues, both B forms, a panel count that is not a multiple of the grid."""
+    four epilogues, both B forms, a panel count that is not a multiple of the grid (900 panels on 512 resident blocks: the
+    launcher takes the kernel only when the last round of blocks is at least 85 % full, which 1064 panels were not)."""
     rng = np.random.default_rng(M + N * 3 + K)
     A, B = _mk(rng, M, K), _mk(rng, K, N)
     bias, X0 = _mk(rng, N), _mk(rng, M, N)
@@ -324,13 +401,18 @@ def test_gemm_panel_kernel(ops, M, N, K, tb, monkeypatch):
     ws = ops.Workspace(DEV)
     want = A.astype(np.float64) @ B.astype(np.float64)
     bound = 4e-7 * (np.abs(A).astype(np.float64) @ np.abs(B).astype(np.float64))
+    # the bf16 x 3 kernel is asked before the panel kernel and takes these shapes at K >= 64: off (read per call), or both
+    # legs below run that kernel and compare it with itself — the route of each leg is asserted
+    monkeypatch.setenv("REC_GEMM_BF16X3", "0")
     for kw, ref, extra in ((dict(), want, 0.0), (dict(epilogue="bias", bias=t(bias)), want + bias, 1e-6),
                            (dict(epilogue="bias_relu", bias=t(bias)), np.maximum(want + bias, 0), 1e-6),
                            (dict(epilogue="relu_mask", aux0=t(X0)), np.where(X0 > 0, want, 0), 0.0)):
         monkeypatch.setenv("REC_GEMM_PANEL", "1")
         Cp = ops.gemm(At, Bt, ws, trans_b=tb, **kw).cpu().numpy()
+        _took(ops, "panel")
         monkeypatch.setenv("REC_GEMM_PANEL", "0")
         Ct = ops.gemm(At, Bt, ws, trans_b=tb, **kw).cpu().numpy()
+        assert ops.gemm_last_route().family in ("tiled", "glds")     # (N = 432 is three 144-column blocks of the ring)
         _check(Cp, ref, bound + extra)
         assert np.array_equal(Cp, Ct), kw.get("epilogue", "none")
 
@@ -412,36 +494,14 @@ def test_gemm_bf16x3(ops, monkeypatch, M, N, K, tb, epi):
               aux1=t(X1) if epi in ("cross", "add", "moe") else None, row_scale=t(rs) if epi == "moe" else None)
     monkeypatch.setenv("REC_GEMM_BF16X3", "0")
     C0 = ops.gemm(At, Bt, ops.Workspace(DEV), **kw).cpu().numpy()
+    assert ops.gemm_last_route().family in ("tiled", "glds")       # an exact-f32 kernel
     monkeypatch.setenv("REC_GEMM_BF16X3", "1")
     ws = ops.Workspace(DEV)
     C1 = ops.gemm(At, Bt, ws, **kw).cpu().numpy()
-    acc = A.astype(np.float64) @ B.astype(np.float64)
-    bound = 4e-7 * (np.abs(A).astype(np.float64) @ np.abs(B).astype(np.float64))
-    if epi.startswith("bias"):
-        acc = acc + bias
-        bound = bound + 1.2e-7 * np.abs(acc)                 # the f32 add of the bias
-    if epi == "bias_relu":
-        acc = np.maximum(acc, 0)
-    if epi == "relu_mask":
-        acc = np.where(X0 > 0, acc, 0)
-    if epi == "cross":                                       # dcn_v2/net.py:225: X_l + X_0 * (X_l W + b)
-        acc = X1 + X0.astype(np.float64) * (acc + bias)
-        bound = bound * np.abs(X0) + 2.4e-7 * (np.abs(acc) + np.abs(X1)) + 1e-7
-    if epi == "add":
-        acc = acc + bias + X1.astype(np.float64) + X0
-        bound = bound + 3.6e-7 * (np.abs(acc) + np.abs(X1) + np.abs(X0)) + 1e-7
-    if epi == "moe":                                         # x_l + x_0 * gate_e * (U_e v + b)
-        acc = X1 + X0.astype(np.float64) * rs[:, None] * (acc + bias)
-        bound = bound * np.abs(X0 * rs[:, None]) + 3.6e-7 * (np.abs(acc) + np.abs(X1)) + 1e-7
-    if epi in ("bias_tanh", "bias_sigmoid"):                 # expf / tanhf of the device: a few ulp of the result
-        acc = np.tanh(acc) if epi == "bias_tanh" else 1.0 / (1.0 + np.exp(-acc))
-        bound = bound + 1e-6
-    if epi == "dtanh":
-        acc = acc * (1.0 - X0.astype(np.float64) ** 2)
-        bound = bound * np.abs(1.0 - X0.astype(np.float64) ** 2) + 2.4e-7 * np.abs(acc) + 1e-7
-    if epi == "dsigmoid":
-        acc = acc * X0.astype(np.float64) * (1.0 - X0)
-        bound = bound * np.abs(X0 * (1.0 - X0)) + 3.6e-7 * np.abs(acc) + 1e-7
+    _took(ops, "x3")
+    given = lambda name, a: a if kw[name] is not None else None
+    acc, bound = gemm_ref.epi_reference(epi, A, B, given("bias", bias), given("aux0", X0), given("aux1", X1),
+                                        given("row_scale", rs))
     _check(C1, acc, bound)
     _check(C0, acc, bound)
     assert not np.array_equal(C0, C1), "REC_GEMM_BF16X3=1 did not select the bf16 x 3 kernel"
