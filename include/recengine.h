@@ -1429,6 +1429,46 @@ int rec_dcn_cross_bwd(const rec_dcn_cross_desc* desc, const float* X0, const flo
                       const float* saved, const float* dXL, const float* dz, const float* u, float* dX0, float* d_w,
                       float* d_b, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * GateNet: the embedding gate and the hidden gate of models/rank/gatenet/net.py:88-118.
+ * Embedding gate, field s of S, e = W[id] (D floats), ONE scalar weight w_s per field:
+ *   t = sum_k e_k,   a = sigmoid(w_s * t),   out = e * a
+ * Lookup i of n = B * S (field s = i % S, sample i / S) lives at  base + (i / S) * stride + s * D  (floats) on the
+ * output side — the head of a feature row of S*D + Dn floats, whose dense columns and padding floats are never
+ * touched.  An id outside [0, num_rows) gives a zero row and raises REC_FLAG_INDEX_OOB in *status; id == padding_idx
+ * (-1: none) gives a zero row.  Rows whose base addresses and strides (table and output) are multiples of 16 bytes move
+ * as 16-byte vectors when emb_dim % 4 == 0, anything else lane by lane.  n must be a multiple of num_fields, the output
+ * stride at least num_fields * emb_dim: otherwise REC_EINVAL before any launch.  n == 0 launches nothing.  Exact f32.
+ * ---------------------------------------------------------------------------------------- */
+int rec_gate_emb_fwd(int64_t n, int32_t num_fields, int32_t emb_dim, int32_t row_stride, int64_t num_rows,
+                     int64_t padding_idx, const int64_t* ids, const float* W, const float* gate_w, float* out,
+                     int64_t out_stride, int32_t* status, void* stream);
+/* Bytes of `workspace` for rec_gate_emb_bwd: its per-block partials of d_gate_w (at most 2048 blocks of num_fields). */
+int rec_gate_emb_bwd_workspace_bytes(int64_t n, int32_t num_fields, size_t* bytes);
+/* Backward of the gate, IN PLACE on g (the layout of `out` above, stride g_stride): on entry g = dloss / d out, on
+ * return g = dloss / d e.  e is gathered again from W (not yet updated), t and a are recomputed:
+ *   da = <g, e>,   dp = da * a * (1 - a),   d e_k = g_k * a + dp * w_s,   d_gate_w[s] = sum over the batch of dp * t
+ * Padding and out-of-range lookups get a zero row (the latter raise the flag).  d_gate_w [num_fields] is summed without
+ * float atomics — per-block partials over fixed lookup ranges, folded in block order — so two runs are bit-identical;
+ * n == 0 writes zeros to it (when non-NULL).  num_fields <= 1024. */
+int rec_gate_emb_bwd(int64_t n, int32_t num_fields, int32_t emb_dim, int32_t row_stride, int64_t num_rows,
+                     int64_t padding_idx, const int64_t* ids, const float* W, const float* gate_w, float* g,
+                     int64_t g_stride, float* d_gate_w, int32_t* status, void* workspace, size_t workspace_bytes,
+                     void* stream);
+/* Hidden gate x = y * tanh(y @ G), elementwise over [batch, n] with row strides ld_* (floats, >= n); the two GEMMs
+ * around it are rec_gemm_f32 calls.  Forward: t = y @ G on entry; x = y * tanh(t) is written and t is overwritten with
+ * h = tanh(t), which the backward reads. */
+int rec_gate_hidden_fwd(int64_t batch, int32_t n, const float* y, int64_t ld_y, float* t, int64_t ld_t, float* x,
+                        int64_t ld_x, void* stream);
+/* Backward for upstream u = dloss / d x:  dt = u * y * (1 - h^2)  (-> dG = y^T dt, and dt @ G^T into dy)  and the direct
+ * term  uh = u * h.  The outputs alias nothing. */
+int rec_gate_hidden_bwd(int64_t batch, int32_t n, const float* u, int64_t ld_u, const float* y, int64_t ld_y,
+                        const float* h, int64_t ld_h, float* dt, int64_t ld_dt, float* uh, int64_t ld_uh, void* stream);
+/* dy[r,c] = y[r,c] > 0 ? dy[r,c] : 0 — the ReLU in front of the gate; the mask is y's (the gated x can be <= 0 where y
+ * is positive).  Floats between the rows are not touched. */
+int rec_relu_mask_inplace(int64_t batch, int32_t n, float* dy, int64_t ld_dy, const float* y, int64_t ld_y,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -216,6 +216,12 @@ SIGNATURES = {
     "rec_dcn_cross_bwd_workspace_bytes": (C.c_int, [C.POINTER(DcnCrossDesc), C.POINTER(_SZ)]),
     "rec_dcn_cross_fwd": (C.c_int, [C.POINTER(DcnCrossDesc)] + [_P] * 7 + [_SZ, _P]),
     "rec_dcn_cross_bwd": (C.c_int, [C.POINTER(DcnCrossDesc)] + [_P] * 11 + [_SZ, _P]),
+    "rec_gate_emb_fwd": (C.c_int, [_I64, _I32, _I32, _I32, _I64, _I64, _P, _P, _P, _P, _I64, _P, _P]),
+    "rec_gate_emb_bwd_workspace_bytes": (C.c_int, [_I64, _I32, C.POINTER(_SZ)]),
+    "rec_gate_emb_bwd": (C.c_int, [_I64, _I32, _I32, _I32, _I64, _I64, _P, _P, _P, _P, _I64, _P, _P, _P, _SZ, _P]),
+    "rec_gate_hidden_fwd": (C.c_int, [_I64, _I32, _P, _I64, _P, _I64, _P, _I64, _P]),
+    "rec_gate_hidden_bwd": (C.c_int, [_I64, _I32, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P]),
+    "rec_relu_mask_inplace": (C.c_int, [_I64, _I32, _P, _I64, _P, _I64, _P]),
     "rec_dense_fold_fwd": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P]),
     "rec_dense_fold_bwd": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _I32, _P]),
     "rec_dense_fold_fwd_full": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P]),

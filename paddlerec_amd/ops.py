@@ -619,6 +619,99 @@ def dcn_cross_bwd(x0, w, b, saved, dxl, ws, l2_coeff=1.0, accumulate=False, out=
     return dx0, d_w, d_b
 
 
+# ------------------------------------------------------------------ GateNet gates (rank/gatenet)
+def _gate_emb_args(ids, W, gate_w, what):
+    """Checks shared by gate_emb_fwd / gate_emb_bwd -> (B, S, D, table row stride, N)."""
+    _chk(ids, torch.int64, "ids")
+    if ids.dim() != 2 or ids.shape[1] < 1:
+        raise RecError("%s: ids must be [B, S]" % what)
+    B, S = ids.shape
+    _, w_stride = _chk_table(W, "W")
+    if W.dim() != 2:
+        raise RecError("%s: W must be [N, D]" % what)
+    N, D = W.shape
+    _chk(gate_w, torch.float32, "gate_w")
+    if gate_w.numel() != S:
+        raise RecError("%s: gate_w must hold S = %d floats (one scalar per field)" % (what, S))
+    return B, S, D, w_stride, N
+
+
+def gate_emb_fwd(ids, W, gate_w, padding_idx=None, status=None, out=None):
+    """Lookup + embedding gate in one pass (rec_gate_emb_fwd): ids [B,S] i64, W [N,D] (rows may be strided), gate_w [S]
+    -> out [B, S*D] with out[b, s*D:(s+1)*D] = e * sigmoid(gate_w[s] * sum(e)), e = W[ids[b,s]].  out may be the head
+    columns of a wider feature buffer (unit column stride; the rest of a row is not touched).  -> (out, status)."""
+    B, S, D, w_stride, N = _gate_emb_args(ids, W, gate_w, "gate_emb_fwd")
+    if out is None:
+        out = torch.empty(B, S * D, dtype=torch.float32, device=ids.device)
+    ld = _dcn_rows(out, B, S * D, "out")
+    if status is None:
+        status = new_status(ids.device)
+    check(lib().rec_gate_emb_fwd(B * S, S, D, w_stride, N, -1 if padding_idx is None else padding_idx, _p(ids), _p(W),
+                                 _p(gate_w), _p(out), ld, _p(status), _stream()), "rec_gate_emb_fwd")
+    return out, status
+
+
+def gate_emb_bwd(ids, W, gate_w, g, ws, padding_idx=None, status=None, out=None):
+    """Backward of gate_emb_fwd IN PLACE (rec_gate_emb_bwd): g [B, S*D] (a view as `out` there) holds dloss / d out on
+    entry and dloss / d e on return; W must still hold the forward's rows.  -> (g, d_gate_w [S] = out or a new tensor,
+    status).  d_gate_w is a fixed-order sum: reruns are bit-identical."""
+    B, S, D, w_stride, N = _gate_emb_args(ids, W, gate_w, "gate_emb_bwd")
+    ld = _dcn_rows(g, B, S * D, "g")
+    if out is None:
+        out = torch.empty(S, dtype=torch.float32, device=ids.device)
+    _chk(out, torch.float32, "d_gate_w")
+    if out.numel() != S:
+        raise RecError("gate_emb_bwd: d_gate_w must hold S = %d floats" % S)
+    if status is None:
+        status = new_status(ids.device)
+    nbytes = C.c_size_t(0)
+    check(lib().rec_gate_emb_bwd_workspace_bytes(B * S, S, C.byref(nbytes)), "rec_gate_emb_bwd_workspace_bytes")
+    wk = ws.get(nbytes.value)
+    check(lib().rec_gate_emb_bwd(B * S, S, D, w_stride, N, -1 if padding_idx is None else padding_idx, _p(ids), _p(W),
+                                 _p(gate_w), _p(g), ld, _p(out), _p(status), _p(wk), C.c_size_t(wk.numel()), _stream()),
+          "rec_gate_emb_bwd")
+    return g, out, status
+
+
+def _gate_rows(ts, what):
+    """Float32 device matrices of ONE shape [B, n] with unit column stride -> (B, n, their row strides)."""
+    B, n = ts[0][0].shape if torch.is_tensor(ts[0][0]) and ts[0][0].dim() == 2 else (-1, -1)
+    if B < 0 or n < 1:
+        raise RecError("%s: %s must be a matrix [B, n] with n >= 1" % (what, ts[0][1]))
+    return B, n, [_dcn_rows(t, B, n, name) for t, name in ts]
+
+
+def gate_hidden_fwd(y, t, out=None):
+    """x = y * tanh(t) for t = y @ G (rec_gate_hidden_fwd); t is overwritten with h = tanh(t).  -> (x, h)."""
+    if out is None:
+        out = torch.empty(tuple(y.shape), dtype=torch.float32, device=y.device) if torch.is_tensor(y) else None
+    B, n, (ld_y, ld_t, ld_x) = _gate_rows([(y, "y"), (t, "t"), (out, "x")], "gate_hidden_fwd")
+    check(lib().rec_gate_hidden_fwd(B, n, _p(y), ld_y, _p(t), ld_t, _p(out), ld_x, _stream()), "rec_gate_hidden_fwd")
+    return out, t
+
+
+def gate_hidden_bwd(u, y, h, out=None):
+    """Upstream u = dloss / d x, the forward's y and h -> (dt = u * y * (1 - h^2), uh = u * h) (rec_gate_hidden_bwd).
+    out = (dt, uh), new tensors where None."""
+    dt, uh = out if out is not None else (None, None)
+    if torch.is_tensor(u) and u.dim() == 2:
+        if dt is None:
+            dt = torch.empty(tuple(u.shape), dtype=torch.float32, device=u.device)
+        if uh is None:
+            uh = torch.empty(tuple(u.shape), dtype=torch.float32, device=u.device)
+    B, n, ld = _gate_rows([(u, "u"), (y, "y"), (h, "h"), (dt, "dt"), (uh, "uh")], "gate_hidden_bwd")
+    check(lib().rec_gate_hidden_bwd(B, n, _p(u), ld[0], _p(y), ld[1], _p(h), ld[2], _p(dt), ld[3], _p(uh), ld[4],
+                                    _stream()), "rec_gate_hidden_bwd")
+    return dt, uh
+
+
+def relu_mask_(dy, y):
+    """dy *= (y > 0) in place (rec_relu_mask_inplace); floats between the rows of a strided dy keep their values."""
+    B, n, (ld_dy, ld_y) = _gate_rows([(dy, "dy"), (y, "y")], "relu_mask_")
+    check(lib().rec_relu_mask_inplace(B, n, _p(dy), ld_dy, _p(y), ld_y, _stream()), "rec_relu_mask_inplace")
+    return dy
+
+
 def dense_fold_fwd(S, dense_w, W0, M):
     """M[j,:] = dense_w[j,:] @ W0[(S+j)*D:(S+j+1)*D, :]   (dense embeddings folded into MLP layer 0)."""
     Dn, D = dense_w.shape[-2], dense_w.shape[-1]

@@ -10,7 +10,7 @@ What differs by construction: a batch never becomes 28 per-sample NumPy arrays (
 [B,26] / [B,13] device tensors), `loss.backward(); optimizer.step()` is the explicit `train_step` chain of the
 host mirrors, and the AUC buckets stay on the device (read back only when a log line prints them).
 
-    python -m paddlerec_amd.trainer -m <config.yaml> [--model deepfm|fm|ffm|deepfefm|wide_deep|dnn|dcn|dcn_v2|din|xdeepfm|dlrm] [-o runner.epochs=1 ...] [--infer]
+    python -m paddlerec_amd.trainer -m <config.yaml> [--model deepfm|fm|ffm|deepfefm|wide_deep|dnn|dcn|dcn_v2|gatenet|din|xdeepfm|dlrm] [-o runner.epochs=1 ...] [--infer]
     python -m torch.distributed.run --nproc-per-node G -m paddlerec_amd.trainer -m <config.yaml>     # collective mode
 """
 import argparse
@@ -24,7 +24,7 @@ from . import checkpoint
 
 logger = logging.getLogger("paddlerec_amd.trainer")
 
-MODELS = ("deepfm", "fm", "ffm", "deepfefm", "wide_deep", "dnn", "dcn", "dcn_v2", "din", "xdeepfm", "dlrm")
+MODELS = ("deepfm", "fm", "ffm", "deepfefm", "wide_deep", "dnn", "dcn", "dcn_v2", "gatenet", "din", "xdeepfm", "dlrm")
 
 
 # ------------------------------------------------------------------------------------ configuration
@@ -87,6 +87,8 @@ def _dygraph_model(name):
         from .dcn import DygraphModel
     elif name == "dcn_v2":
         from .dcn_v2 import DygraphModel
+    elif name == "gatenet":
+        from .gatenet import DygraphModel
     elif name == "din":
         from .din import DygraphModel
     elif name == "xdeepfm":
@@ -234,6 +236,11 @@ def _apply_optimizer_config(config, model, dy_model):
                     "the batch (not a mean), coefficient 1 (dcn/dygraph_model.py:98); hyper_parameters.l2_reg_cross=%s and "
                     "clip_by_norm=%s are read and stored as in the reference and, as there, never used",
                     getattr(dy_model, "l2_reg_cross", None), getattr(dy_model, "clip_by_norm", None))
+    if model == "gatenet":
+        logger.info("gatenet: the embedding gate's weight is ONE scalar per field, as in the reference (gatenet/net.py:34-38, "
+                    "shape=[1]; the GateNet paper has a vector): a lookup is scaled by sigmoid(w_s * sum_k e_k); the table has "
+                    "no padding row (id 0 trains); use_embedding_gate=%s, use_hidden_gate=%s",
+                    getattr(dy_model, "use_embedding_gate", None), getattr(dy_model, "use_hidden_gate", None))
     if model == "dcn_v2":
         logger.info("dcn_v2 train mode: Dropout(%.2f) after every element of the DNN tower (dcn_v2/net.py:181-183) with the "
                     "engine's counter-based masks (seed %d; Paddle's own mask stream is not reproducible), L2Decay(%g) on "
