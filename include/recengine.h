@@ -1341,6 +1341,49 @@ int rec_ffm_bwd(const rec_ffm_desc* desc, const int64_t* ids, const float* dense
                 void* workspace, size_t workspace_bytes, int32_t* status, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * FAT-DeepFFM: CENet attention over the cube slices + attention-scaled field-pair Hadamard features,
+ * models/rank/fat_deepffm/net.py:105-151 (CENLayer.forward) and :219-251 (DeepFFM.forward, is_H).
+ * The cube E, F and R are FFM's (above), as are the limits (F <= 64, dim <= 32: REC_ESHAPE before any launch) and the
+ * handling of an id outside [0, num_rows).  F2 = F*F slices q = i*F + j with mirror q' = j*F + i; P = F (F - 1) / 2
+ * pairs p = (i, j), i < j, in nested-loop order.
+ *   pooled[b,q]    = max_d E[q, d]
+ *   (the caller:     a = relu(relu(pooled @ W_red + b_red) @ W_add + b_add), two GEMMs)
+ *   y1[b]          = sum_q a[b,q] * sum_d E[q, d]                     (the diagonal slices included)
+ *   H[b, p*dim+d]  = a[b,q] E[q, d] * a[b,q'] E[q', d]
+ * Backward for dz [B] = dloss/dlogit and dH = dloss/dH:
+ *   t[q, d]        = dz + dH[p*dim+d] * a[q'] * E[q', d]  (i != j),   dz  (i == j)
+ *   d_a[b,q]       = sum_d E[q, d] * t[q, d]
+ *   dE[q, d]       = a[q] * t[q, d] + (d == argmax_d E[q, :]) * d_pooled[b,q]
+ * The argmax is the smallest d among equal maxima; it is recomputed from the cube (no index tensor is stored).
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+  rec_ffm_desc ffm;   /* grad_stride is read by rec_fatffm_bwd only */
+  int64_t ld_attn;    /* floats between consecutive rows of pooled / a / d_a / d_pooled (>= F2) */
+  int64_t ld_pair;    /* floats between consecutive rows of H / dH (>= P*dim) */
+} rec_fatffm_desc;
+
+/* ids [B,S] i64; dense [B,Dn]; W [N,row_stride]; dense_w [Dn,R] -> pooled [B,ld_attn] */
+int rec_fatffm_pool_fwd(const rec_fatffm_desc* desc, const int64_t* ids, const float* dense, const float* W,
+                        const float* dense_w, float* pooled, int32_t* status, void* stream);
+/* the same inputs + a [B,ld_attn] -> H [B,ld_pair], y1 [B].  The rows are gathered again: the cube is never stored. */
+int rec_fatffm_inter_fwd(const rec_fatffm_desc* desc, const int64_t* ids, const float* dense, const float* W,
+                         const float* dense_w, const float* a, float* H, float* y1, int32_t* status, void* stream);
+/* the inputs + a, dH [B,ld_pair], dz [B] -> d_a [B,ld_attn] (before the ReLU mask a > 0, which is the caller's) */
+int rec_fatffm_attn_bwd(const rec_fatffm_desc* desc, const int64_t* ids, const float* dense, const float* W,
+                        const float* dense_w, const float* a, const float* dH, const float* dz, float* d_a,
+                        int32_t* status, void* stream);
+/* the inputs + a, dH, dz, d_pooled [B,ld_attn] ->
+ *   row_grad [B*S, grad_stride] — SelectedRows.value of `embedding`, unmerged, in position order: row b*S+i = dE_b[i],
+ *     written once and complete, 0 on the pad columns [R, grad_stride);
+ *   d_dense_w [Dn,R] = sum_b dense[b,k] * dE_b[S+k] — per-block partials folded in block order (two runs are
+ *     bit-identical). */
+int rec_fatffm_bwd_workspace_bytes(const rec_fatffm_desc* desc, size_t* bytes);
+int rec_fatffm_bwd(const rec_fatffm_desc* desc, const int64_t* ids, const float* dense, const float* W,
+                   const float* dense_w, const float* a, const float* dH, const float* dz, const float* d_pooled,
+                   float* row_grad, float* d_dense_w, void* workspace, size_t workspace_bytes, int32_t* status,
+                   void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * FEFM: field-embedded factorisation machine, models/rank/deepfefm/net.py:118-187 (FEFM.forward).
  * F = num_slots + num_dense fields, P = F (F - 1) / 2 pairs p = (i, j), i < j, in itertools.combinations order.
  *   id[b,f]   = ids[b,f] (f < S),  int64(dense[b,f-S] * 1e5 + 1e6 + 2) (f >= S: three rounded f32 operations, truncated)

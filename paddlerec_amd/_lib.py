@@ -29,6 +29,11 @@ class FFMDesc(C.Structure):
                 ("num_rows", C.c_int64), ("row_stride", C.c_int32), ("grad_stride", C.c_int32)]
 
 
+class FatFFMDesc(C.Structure):
+    """rec_fatffm_desc (include/recengine.h)."""
+    _fields_ = [("ffm", FFMDesc), ("ld_attn", C.c_int64), ("ld_pair", C.c_int64)]
+
+
 class FEFMDesc(C.Structure):
     """rec_fefm_desc (include/recengine.h)."""
     _fields_ = [("batch", C.c_int64), ("num_slots", C.c_int32), ("num_dense", C.c_int32), ("dim", C.c_int32),
@@ -209,6 +214,11 @@ SIGNATURES = {
     "rec_ffm_fwd": (C.c_int, [C.POINTER(FFMDesc)] + [_P] * 10),
     "rec_ffm_bwd_workspace_bytes": (C.c_int, [C.POINTER(FFMDesc), C.POINTER(_SZ)]),
     "rec_ffm_bwd": (C.c_int, [C.POINTER(FFMDesc)] + [_P] * 9 + [_SZ, _P, _P]),
+    "rec_fatffm_pool_fwd": (C.c_int, [C.POINTER(FatFFMDesc)] + [_P] * 7),
+    "rec_fatffm_inter_fwd": (C.c_int, [C.POINTER(FatFFMDesc)] + [_P] * 9),
+    "rec_fatffm_attn_bwd": (C.c_int, [C.POINTER(FatFFMDesc)] + [_P] * 10),
+    "rec_fatffm_bwd_workspace_bytes": (C.c_int, [C.POINTER(FatFFMDesc), C.POINTER(_SZ)]),
+    "rec_fatffm_bwd": (C.c_int, [C.POINTER(FatFFMDesc)] + [_P] * 11 + [_SZ, _P, _P]),
     "rec_fefm_fwd_workspace_bytes": (C.c_int, [C.POINTER(FEFMDesc), C.POINTER(_SZ)]),
     "rec_fefm_fwd": (C.c_int, [C.POINTER(FEFMDesc)] + [_P] * 11 + [_SZ, _P, _P]),
     "rec_fefm_bwd_workspace_bytes": (C.c_int, [C.POINTER(FEFMDesc), _I32, C.POINTER(_SZ)]),

@@ -11,7 +11,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import (EPI, AdagradHyper, AdamHyper, CinView, DcnCrossDesc, DeepFMDesc, DinDesc, FEFMDesc, FFMDesc, GemmBImage, GemmDesc, GemmEpilogueArgs, GradLayout,
+from ._lib import (EPI, AdagradHyper, AdamHyper, CinView, DcnCrossDesc, DeepFMDesc, DinDesc, FatFFMDesc, FEFMDesc, FFMDesc, GemmBImage, GemmDesc, GemmEpilogueArgs, GradLayout,
                    GradSrc, LazyInit, MultislotDesc, PsAccessor, PsLayout, RecError, check)
 
 _recorder = None        # paddlerec_amd.plan.CallPlan while a step is being recorded
@@ -401,6 +401,117 @@ def ffm_bwd(ids, dense, W, dense_w, dz, dim, ws, out=None, status=None, grad_str
     check(lib().rec_ffm_bwd(C.byref(desc), _p(ids), _p(dense), _p(W), _p(dense_w), _p(dz), _p(row_grad), _p(d_dense_w),
                             _p(d_dense_w_one), _p(w), C.c_size_t(w.numel()), _p(status), _stream()), "rec_ffm_bwd")
     return row_grad, d_dense_w, d_dense_w_one
+
+
+# ------------------------------------------------------------------ FAT-DeepFFM CENet / field-pair kernels (fat_deepffm)
+def _fat_mat(t, B, cols, name, what):
+    """A [B, >= cols] float32 device matrix with unit column stride (a padded row stride is fine) -> leading dimension."""
+    if t.dim() != 2 or t.dtype != torch.float32 or not t.is_cuda or t.shape[0] != B or t.shape[1] < cols or \
+            (t.shape[1] > 1 and t.stride(1) != 1):
+        raise RecError("%s: %s must be a float32 device matrix [B, >= %d] with unit column stride" % (what, name, cols))
+    return max(t.stride(0), cols) if B > 1 else max(t.shape[1], cols)
+
+
+def _fat_out(out, B, cols, dev):
+    return out if out is not None else torch.empty(B, cols, dtype=torch.float32, device=dev)
+
+
+def _fat_desc(ids, dense, W, dense_w, dim, what, attn=(), pair=(), grad_stride=0):
+    """attn / pair: (tensor, name) matrices that share ld_attn / ld_pair."""
+    B, S, Dn, R, stride = _ffm_desc(ids, dense, dim, W, what)
+    _chk(dense_w, torch.float32, "dense_w")
+    if dense_w.numel() != Dn * R:
+        raise RecError("%s: dense_w must hold Dn x R floats" % what)
+    F = S + Dn
+    lds = []
+    for mats, cols in ((attn, F * F), (pair, F * (F - 1) // 2 * int(dim))):
+        ld = {_fat_mat(t, B, cols, n, what) for t, n in mats}
+        if len(ld) > 1:
+            raise RecError("%s: %s must share one leading dimension" % (what, " / ".join(n for _, n in mats)))
+        lds.append(ld.pop() if ld else cols)
+    return FatFFMDesc(FFMDesc(B, S, Dn, int(dim), W.shape[0], stride, int(grad_stride)), lds[0], lds[1]), B, S, Dn, R
+
+
+def fatffm_pool_fwd(ids, dense, W, dense_w, dim, status=None, out=None):
+    """ids [B,S] i64, dense [B,Dn] f32, W [N, >= R] (R = (S+Dn)*dim), dense_w [Dn,R]|[1,Dn,R] -> pooled [B, F*F] (or the
+    wider-rowed matrix given as out: its row stride is used), status  (rec_fatffm_pool_fwd)."""
+    F = ids.shape[1] + dense.shape[1]
+    pooled = _fat_out(out, ids.shape[0], F * F, ids.device)
+    desc, B, S, Dn, R = _fat_desc(ids, dense, W, dense_w, dim, "fatffm_pool_fwd", attn=[(pooled, "pooled")])
+    if status is None:
+        status = new_status(ids.device)
+    check(lib().rec_fatffm_pool_fwd(C.byref(desc), _p(ids), _p(dense), _p(W), _p(dense_w), _p(pooled), _p(status),
+                                    _stream()), "rec_fatffm_pool_fwd")
+    return pooled, status
+
+
+def fatffm_inter_fwd(ids, dense, W, dense_w, a, dim, status=None, out=None):
+    """+ a [B, F*F] -> H [B, P*dim] (P = F(F-1)/2; or the wider-rowed matrix given as out[0]), y1 [B,1], status
+    (rec_fatffm_inter_fwd)."""
+    B, F = ids.shape[0], ids.shape[1] + dense.shape[1]
+    H, y1 = out if out is not None else (None, None)
+    H = _fat_out(H, B, F * (F - 1) // 2 * int(dim), ids.device)
+    if y1 is None:
+        y1 = torch.empty(B, 1, dtype=torch.float32, device=ids.device)
+    _chk(y1, torch.float32, "y1")
+    if y1.numel() != B:
+        raise RecError("fatffm_inter_fwd: y1 must hold B values")
+    desc, B, S, Dn, R = _fat_desc(ids, dense, W, dense_w, dim, "fatffm_inter_fwd", attn=[(a, "a")], pair=[(H, "H")])
+    if status is None:
+        status = new_status(ids.device)
+    check(lib().rec_fatffm_inter_fwd(C.byref(desc), _p(ids), _p(dense), _p(W), _p(dense_w), _p(a), _p(H), _p(y1),
+                                     _p(status), _stream()), "rec_fatffm_inter_fwd")
+    return H, y1, status
+
+
+def fatffm_attn_bwd(ids, dense, W, dense_w, a, dH, dz, dim, status=None, out=None):
+    """+ dH [B, P*dim] = dloss / dH, dz [B]|[B,1] = dloss / dlogit -> d_a [B, F*F] (row stride of a), status
+    (rec_fatffm_attn_bwd)."""
+    B, F = ids.shape[0], ids.shape[1] + dense.shape[1]
+    d_a = out if out is not None else torch.empty_like(a)
+    _chk(dz, torch.float32, "dz")
+    if dz.numel() != B:
+        raise RecError("fatffm_attn_bwd: dz must hold B values")
+    desc, B, S, Dn, R = _fat_desc(ids, dense, W, dense_w, dim, "fatffm_attn_bwd", attn=[(a, "a"), (d_a, "d_a")],
+                                  pair=[(dH, "dH")])
+    if status is None:
+        status = new_status(ids.device)
+    check(lib().rec_fatffm_attn_bwd(C.byref(desc), _p(ids), _p(dense), _p(W), _p(dense_w), _p(a), _p(dH), _p(dz),
+                                    _p(d_a), _p(status), _stream()), "rec_fatffm_attn_bwd")
+    return d_a, status
+
+
+def fatffm_bwd(ids, dense, W, dense_w, a, dH, dz, d_pooled, dim, ws, out=None, status=None, grad_stride=None):
+    """+ d_pooled [B, F*F] (row stride of a) -> row_grad [B*S, grad_stride] (default: R rounded up to 4 floats; the pad
+    columns are 0), d_dense_w [Dn,R], status  (rec_fatffm_bwd)."""
+    B, S = ids.shape
+    Dn = dense.shape[1]
+    R = (S + Dn) * int(dim)
+    gs = int(grad_stride) if grad_stride else (R + 3) // 4 * 4
+    _chk(dz, torch.float32, "dz")
+    if dz.numel() != B:
+        raise RecError("fatffm_bwd: dz must hold B values")
+    desc, B, S, Dn, R = _fat_desc(ids, dense, W, dense_w, dim, "fatffm_bwd", attn=[(a, "a"), (d_pooled, "d_pooled")],
+                                  pair=[(dH, "dH")], grad_stride=gs)
+    dev = ids.device
+    row_grad, d_dense_w = out if out is not None else (None, None)
+    if row_grad is None:
+        row_grad = torch.empty(B * S, gs, dtype=torch.float32, device=dev)
+    if d_dense_w is None:
+        d_dense_w = torch.empty(Dn, R, dtype=torch.float32, device=dev)
+    _chk(row_grad, torch.float32, "row_grad", (B * S, gs))
+    _chk(d_dense_w, torch.float32, "d_dense_w")
+    if d_dense_w.numel() != Dn * R:
+        raise RecError("fatffm_bwd: d_dense_w must hold Dn x R floats")
+    if status is None:
+        status = new_status(dev)
+    nbytes = C.c_size_t(0)
+    check(lib().rec_fatffm_bwd_workspace_bytes(C.byref(desc), C.byref(nbytes)), "rec_fatffm_bwd_workspace_bytes")
+    w = ws.get(nbytes.value)
+    check(lib().rec_fatffm_bwd(C.byref(desc), _p(ids), _p(dense), _p(W), _p(dense_w), _p(a), _p(dH), _p(dz),
+                               _p(d_pooled), _p(row_grad), _p(d_dense_w), _p(w), C.c_size_t(w.numel()), _p(status),
+                               _stream()), "rec_fatffm_bwd")
+    return row_grad, d_dense_w, status
 
 
 # ------------------------------------------------------------------ FEFM field-pair bilinear interaction (deepfefm)

@@ -10,7 +10,7 @@ What differs by construction: a batch never becomes 28 per-sample NumPy arrays (
 [B,26] / [B,13] device tensors), `loss.backward(); optimizer.step()` is the explicit `train_step` chain of the
 host mirrors, and the AUC buckets stay on the device (read back only when a log line prints them).
 
-    python -m paddlerec_amd.trainer -m <config.yaml> [--model deepfm|fm|ffm|deepfefm|wide_deep|dnn|dcn|dcn_v2|gatenet|din|xdeepfm|dlrm] [-o runner.epochs=1 ...] [--infer]
+    python -m paddlerec_amd.trainer -m <config.yaml> [--model deepfm|fm|ffm|deepfefm|fat_deepffm|wide_deep|dnn|dcn|dcn_v2|gatenet|din|xdeepfm|dlrm] [-o runner.epochs=1 ...] [--infer]
     python -m torch.distributed.run --nproc-per-node G -m paddlerec_amd.trainer -m <config.yaml>     # collective mode
 """
 import argparse
@@ -24,7 +24,7 @@ from . import checkpoint
 
 logger = logging.getLogger("paddlerec_amd.trainer")
 
-MODELS = ("deepfm", "fm", "ffm", "deepfefm", "wide_deep", "dnn", "dcn", "dcn_v2", "gatenet", "din", "xdeepfm", "dlrm")
+MODELS = ("deepfm", "fm", "ffm", "deepfefm", "fat_deepffm", "wide_deep", "dnn", "dcn", "dcn_v2", "gatenet", "din", "xdeepfm", "dlrm")
 
 
 # ------------------------------------------------------------------------------------ configuration
@@ -79,6 +79,8 @@ def _dygraph_model(name):
         from .ffm import DygraphModel
     elif name == "deepfefm":
         from .deepfefm import DygraphModel
+    elif name == "fat_deepffm":
+        from .fat_deepffm import DygraphModel
     elif name == "wide_deep":
         from .wide_deep import DygraphModel
     elif name == "dnn":
@@ -231,6 +233,13 @@ def _apply_optimizer_config(config, model, dy_model):
         logger.info("deepfefm train mode: Dropout(%.2f) after every element of the DNN's layer list, the last Linear "
                     "included (deepfefm/net.py:229-234), with the engine's counter-based masks (seed %d)",
                     getattr(dy_model, "dropout_rate", 0.0), getattr(dy_model, "dropout_seed", 0))
+    if model == "fat_deepffm":
+        logger.info("fat_deepffm train mode: Dropout(%.2f) after every element of the DNN's layer list, the last Linear's "
+                    "[B,1] output included (fat_deepffm/net.py:200-202), with the engine's counter-based masks (seed %d), "
+                    "L2Decay(%g) on the DNN weights; with the reference's own initialisers and sizes the logit saturates on "
+                    "dense values of order 1 (cen.dense_w starts at 1.0: such a predict is 1.0 in float32 and its gradient "
+                    "0), as in the reference", getattr(dy_model, "dropout_rate", 0.0),
+                    getattr(dy_model, "dropout_seed", 0), getattr(dy_model, "l2_dnn", 0.0))
     if model == "dcn":
         logger.info("dcn: the cross network's l2 term enters the loss as the reference's dygraph path adds it — summed over "
                     "the batch (not a mean), coefficient 1 (dcn/dygraph_model.py:98); hyper_parameters.l2_reg_cross=%s and "
