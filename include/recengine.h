@@ -1512,6 +1512,57 @@ int rec_gate_hidden_bwd(int64_t batch, int32_t n, const float* u, int64_t ld_u, 
 int rec_relu_mask_inplace(int64_t batch, int32_t n, float* dy, int64_t ld_dy, const float* y, int64_t ld_y,
                           void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * FLEN: the field-wise bi-interaction of models/rank/flen/net.py:79, 205-229, fused into the lookup.
+ * ids [batch, num_slots] index ONE table W (raw ids, no padding row).  The slots are partitioned into num_groups field
+ * groups: group g owns the slots [group_begin[g], group_begin[g + 1]); group_begin is a HOST array of num_groups + 1
+ * ints that runs from 0 to num_slots with no empty group (checked before any launch).  2 <= num_groups <=
+ * REC_FLEN_MAX_GROUPS, num_slots >= num_groups, emb_dim >= 1 (<= 64, or <= 256 with emb_dim % 4 == 0), and one sample's
+ * (num_slots + num_groups + 1) * emb_dim floats must fit 64 KB of LDS.  With E[b,s] = W[ids[b,s]] (a zero row for an id
+ * outside [0, num_rows), which raises REC_FLAG_INDEX_OOB in *status) and the pairs p = (i < j) of groups in
+ * itertools.combinations order:
+ *   X0 [batch, x0_stride]      X0[b, s*D:(s+1)*D] = E[b,s]            the DNN input; floats behind S*D are not touched
+ *   FW [batch, num_groups*D]   FW[b,g] = sum of E[b,s] over the slots of group g, in slot order (kept for the backward)
+ *   h_mf [batch, h_stride]     h_mf[b] = sum_p kernel_mf[p] * FW[b,i] * FW[b,j]   (floats behind D are not touched)
+ * kernel_mf [P = num_groups * (num_groups - 1) / 2] is a device pointer.  Rows whose base addresses and strides (table
+ * and X0) are multiples of 16 bytes move as 16-byte vectors when emb_dim % 4 == 0, anything else lane by lane.
+ * batch == 0 launches nothing.  Exact f32, fixed summation order.
+ * ---------------------------------------------------------------------------------------- */
+#define REC_FLEN_MAX_GROUPS 8
+int rec_flen_fwd(int64_t batch, int32_t num_slots, int32_t num_groups, int32_t emb_dim, int32_t row_stride,
+                 int64_t num_rows, const int64_t* ids, const float* W, const int32_t* group_begin, const float* kernel_mf,
+                 float* X0, int64_t x0_stride, float* h_mf, int64_t h_stride, float* FW, int32_t* status, void* stream);
+/* Bytes of `workspace` for rec_flen_bwd: its per-block partials of d_kernel_mf (at most 2048 blocks of P floats). */
+int rec_flen_bwd_workspace_bytes(int64_t batch, int32_t num_slots, int32_t num_groups, int32_t emb_dim, size_t* bytes);
+/* Backward, IN PLACE on g (the layout of X0 above, stride g_stride) and without the table: on entry g = dloss / d X0
+ * (the layer-0 dX), on return the per-lookup row gradient
+ *   g[b,s] = g[b,s] + dH[b] * sum over g' != g(s) of kernel_mf[pair(g(s), g')] * FW[b,g']
+ * where dH [batch, dh_stride] = dloss / d h_mf and FW is the forward's.  An id outside [0, num_rows) gets a zero row
+ * (and raises the flag).  d_kernel_mf[p] = sum over b, d of dH * FW[b,i] * FW[b,j] is summed without float atomics —
+ * per-block partials over fixed sample ranges, folded in block order — so two runs are bit-identical; batch == 0 writes
+ * zeros to it.  g aliases neither FW nor dH. */
+int rec_flen_bwd(int64_t batch, int32_t num_slots, int32_t num_groups, int32_t emb_dim, int64_t num_rows,
+                 const int64_t* ids, const int32_t* group_begin, const float* kernel_mf, const float* FW, const float* dH,
+                 int64_t dh_stride, float* g, int64_t g_stride, float* d_kernel_mf, int32_t* status, void* workspace,
+                 size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * paddle.optimizer.Adagrad [EXT] (flen/dygraph_model.py:68-72):
+ *   acc += g * g;   p -= lr * g / (sqrt(acc) + epsilon)
+ * (not the PS accessor's rule of rec_sparse_adagrad_rows, which keeps one g2sum per row part).  The accumulator starts
+ * at initial_accumulator_value: the caller fills it when it creates it.  g == 0 leaves p and acc bit-unchanged, so
+ * there is no lazy / non-lazy distinction.
+ * rec_adagrad_rows: the rule on the MERGED gradient of every unique row of a grouping (rec_ids_group: duplicates are
+ * summed first, in position order, as Paddle merges a SelectedRows gradient: (sum g)^2, not sum g^2).  Arguments as
+ * rec_sparse_adam_rows: grad_layout may carry the hot-row partials of rec_segment_partials; A [.., state_stride] is the
+ * accumulator table (state_stride <= 0: row_stride).  Untouched rows are not read or written.
+ * rec_adagrad_dense: the rule over n floats of a flat buffer (p, acc and g are three buffers).
+ * ---------------------------------------------------------------------------------------- */
+int rec_adagrad_rows(int64_t n_max, int32_t emb_dim, int32_t row_stride, int32_t state_stride, const int32_t* n_uniq,
+                     const int64_t* uniq_rows, const int32_t* seg_offset, const int32_t* sorted_pos, const float* grad,
+                     const rec_grad_layout* grad_layout, float* P, float* A, float lr, float epsilon, void* stream);
+int rec_adagrad_dense(int64_t n, float* p, float* acc, const float* g, float lr, float epsilon, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

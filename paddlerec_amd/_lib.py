@@ -10,6 +10,7 @@ LIB_PATH = os.path.join(_HERE, "librecengine.so")
 
 REC_FLAG_INDEX_OOB = 1
 REC_FLAG_EXCHANGE_OVERFLOW = 2
+REC_FLEN_MAX_GROUPS = 8
 
 
 class RecError(RuntimeError):
@@ -232,6 +233,13 @@ SIGNATURES = {
     "rec_gate_hidden_fwd": (C.c_int, [_I64, _I32, _P, _I64, _P, _I64, _P, _I64, _P]),
     "rec_gate_hidden_bwd": (C.c_int, [_I64, _I32, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P]),
     "rec_relu_mask_inplace": (C.c_int, [_I64, _I32, _P, _I64, _P, _I64, _P]),
+    "rec_flen_fwd": (C.c_int, [_I64, _I32, _I32, _I32, _I32, _I64, _P, _P, C.POINTER(C.c_int32), _P, _P, _I64, _P, _I64,
+                               _P, _P, _P]),
+    "rec_flen_bwd_workspace_bytes": (C.c_int, [_I64, _I32, _I32, _I32, C.POINTER(_SZ)]),
+    "rec_flen_bwd": (C.c_int, [_I64, _I32, _I32, _I32, _I64, _P, C.POINTER(C.c_int32), _P, _P, _P, _I64, _P, _I64, _P, _P,
+                               _P, _SZ, _P]),
+    "rec_adagrad_rows": (C.c_int, [_I64, _I32, _I32, _I32, _P, _P, _P, _P, _P, C.POINTER(GradLayout), _P, _P, _F, _F, _P]),
+    "rec_adagrad_dense": (C.c_int, [_I64, _P, _P, _P, _F, _F, _P]),
     "rec_dense_fold_fwd": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P]),
     "rec_dense_fold_bwd": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _I32, _P]),
     "rec_dense_fold_fwd_full": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P]),

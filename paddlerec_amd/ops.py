@@ -730,6 +730,100 @@ def dcn_cross_bwd(x0, w, b, saved, dxl, ws, l2_coeff=1.0, accumulate=False, out=
     return dx0, d_w, d_b
 
 
+# ------------------------------------------------------------------ FLEN field-wise bi-interaction (rank/flen)
+def _span(t):
+    """[first byte, one past the last byte) a 2-D view touches."""
+    n = ((t.shape[0] - 1) * t.stride(0) + (t.shape[1] - 1) * t.stride(1) + 1) if t.numel() else 0
+    return t.data_ptr(), t.data_ptr() + 4 * n
+
+
+def _overlap(a, b):
+    (a0, a1), (b0, b1) = _span(a), _span(b)
+    return a0 < b1 and b0 < a1
+
+
+def _flen_args(ids, group_begin, kernel_mf, what):
+    """Checks shared by flen_fwd / flen_bwd -> (B, S, G, the bounds as a C int32 array)."""
+    _chk(ids, torch.int64, "ids")
+    if ids.dim() != 2 or ids.shape[1] < 2:
+        raise RecError("%s: ids must be [B, S] with S >= 2" % what)
+    B, S = ids.shape
+    try:
+        gb = [int(x) for x in group_begin]
+    except TypeError:
+        raise RecError("%s: group_begin must be a sequence of G + 1 ints" % what)
+    G = len(gb) - 1
+    if not 2 <= G <= _lib.REC_FLEN_MAX_GROUPS:
+        raise RecError("%s: group_begin must hold G + 1 bounds for 2 <= G <= %d groups, got %d values"
+                       % (what, _lib.REC_FLEN_MAX_GROUPS, len(gb)))
+    if gb[0] != 0 or gb[-1] != S or any(a >= b for a, b in zip(gb, gb[1:])):
+        raise RecError("%s: group_begin %s must rise strictly from 0 to S = %d" % (what, gb, S))
+    _chk(kernel_mf, torch.float32, "kernel_mf")
+    if kernel_mf is None or kernel_mf.numel() != G * (G - 1) // 2:
+        raise RecError("%s: kernel_mf must hold G (G - 1) / 2 = %d floats" % (what, G * (G - 1) // 2))
+    return B, S, G, (C.c_int32 * (G + 1))(*gb)
+
+
+def flen_fwd(ids, W, group_begin, kernel_mf, status=None, out=None):
+    """Lookup + field-wise bi-interaction in one pass (rec_flen_fwd): ids [B,S] i64, W [N,D] (rows may be strided),
+    group_begin the G + 1 slot bounds of the field groups (host ints), kernel_mf [P] -> X0 [B, S*D] (the lookups side by
+    side), h_mf [B, D] = sum over group pairs of kernel_mf[p] * FW_i * FW_j, FW [B, G*D] (the group sums, contiguous: the
+    backward reads it).  out = (X0, h_mf, FW), new tensors where None; X0 and h_mf may be column blocks of wider buffers
+    (unit column stride; the rest of a row is not touched).  -> (X0, h_mf, FW, status)."""
+    B, S, G, gb = _flen_args(ids, group_begin, kernel_mf, "flen_fwd")
+    _, w_stride = _chk_table(W, "W")
+    if W.dim() != 2:
+        raise RecError("flen_fwd: W must be [N, D]")
+    N, D = W.shape
+    X0, H, FW = out if out is not None else (None, None, None)
+    dev = ids.device
+    if X0 is None:
+        X0 = torch.empty(B, S * D, dtype=torch.float32, device=dev)
+    if H is None:
+        H = torch.empty(B, D, dtype=torch.float32, device=dev)
+    if FW is None:
+        FW = torch.empty(B, G * D, dtype=torch.float32, device=dev)
+    ld_x, ld_h = _dcn_rows(X0, B, S * D, "X0"), _dcn_rows(H, B, D, "h_mf")
+    _chk(FW, torch.float32, "FW", (B, G * D))
+    if _overlap(X0, H) or _overlap(X0, FW) or _overlap(H, FW):
+        raise RecError("flen_fwd: X0, h_mf and FW must not overlap")
+    if status is None:
+        status = new_status(dev)
+    check(lib().rec_flen_fwd(B, S, G, D, w_stride, N, _p(ids), _p(W), gb, _p(kernel_mf), _p(X0), ld_x, _p(H), ld_h,
+                             _p(FW), _p(status), _stream()), "rec_flen_fwd")
+    return X0, H, FW, status
+
+
+def flen_bwd(ids, num_rows, group_begin, kernel_mf, FW, dH, g, ws, status=None, out=None):
+    """Backward of flen_fwd IN PLACE and without the table (rec_flen_bwd): g [B, S*D] (a view as X0 there) holds
+    dloss / d X0 on entry and the per-lookup row gradient on return; dH [B, D] = dloss / d h_mf, FW the forward's.
+    -> (g, d_kernel_mf [P] = out or a new tensor, status).  d_kernel_mf is a fixed-order sum: reruns are bit-identical."""
+    B, S, G, gb = _flen_args(ids, group_begin, kernel_mf, "flen_bwd")
+    P = G * (G - 1) // 2
+    if int(num_rows) < 1:
+        raise RecError("flen_bwd: num_rows must be >= 1")
+    if not torch.is_tensor(dH) or dH.dim() != 2:
+        raise RecError("flen_bwd: dH must be a float32 device matrix [B, D]")
+    D = dH.shape[1]
+    ld_dh, ld_g = _dcn_rows(dH, B, D, "dH"), _dcn_rows(g, B, S * D, "g")
+    _chk(FW, torch.float32, "FW", (B, G * D))
+    if _overlap(g, FW) or _overlap(g, dH):
+        raise RecError("flen_bwd: g must not overlap FW or dH")
+    if out is None:
+        out = torch.empty(P, dtype=torch.float32, device=ids.device)
+    _chk(out, torch.float32, "d_kernel_mf")
+    if out.numel() != P:
+        raise RecError("flen_bwd: d_kernel_mf must hold P = %d floats" % P)
+    if status is None:
+        status = new_status(ids.device)
+    nbytes = C.c_size_t(0)
+    check(lib().rec_flen_bwd_workspace_bytes(B, S, G, D, C.byref(nbytes)), "rec_flen_bwd_workspace_bytes")
+    wk = ws.get(nbytes.value)
+    check(lib().rec_flen_bwd(B, S, G, D, int(num_rows), _p(ids), gb, _p(kernel_mf), _p(FW), _p(dH), ld_dh, _p(g), ld_g,
+                             _p(out), _p(status), _p(wk), C.c_size_t(wk.numel()), _stream()), "rec_flen_bwd")
+    return g, out, status
+
+
 # ------------------------------------------------------------------ GateNet gates (rank/gatenet)
 def _gate_emb_args(ids, W, gate_w, what):
     """Checks shared by gate_emb_fwd / gate_emb_bwd -> (B, S, D, table row stride, N)."""
@@ -1359,6 +1453,39 @@ def adam_dense(p, m, v, g, step, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, grad
     h = _hyper(lr, beta1, beta2, eps, step)
     check(lib().rec_adam_dense(p.numel(), _p(p), _p(m), _p(v), _p(g), _p(grad_scale), C.byref(h),
                                _stream()), "rec_adam_dense")
+
+
+def adagrad_rows(groups, grad, grad_div, P, A, lr, epsilon=1e-6, grad_group=0, grad_group_stride=0, partials=None,
+                 grad_index=None):
+    """paddle.optimizer.Adagrad on the touched rows (rec_adagrad_rows): acc += g*g; p -= lr * g / (sqrt(acc) + epsilon) with
+    g the MERGED gradient of each unique row of `groups`.  A: the accumulator table, the shape of P (created by the caller
+    at initial_accumulator_value).  grad_div / grad_group / grad_group_stride / partials as sparse_adam_rows."""
+    if grad_group <= 0:
+        _chk(grad, torch.float32, "grad")
+    elif not torch.is_tensor(grad) or not grad.is_cuda or grad.dtype != torch.float32:
+        raise RecError("grad must be a float32 device tensor")
+    D, stride = _chk_table(P, "P")
+    if _chk_table(A, "A")[0] != D or A.shape[0] != P.shape[0]:
+        raise RecError("A must have the shape of P")
+    sstride = _chk_table(A, "A")[1]
+    if A.data_ptr() == P.data_ptr():
+        raise RecError("A must not be P")
+    check(lib().rec_adagrad_rows(groups.n, D, stride, sstride, _p(groups.n_uniq), _p(groups.uniq_rows),
+                                 _p(groups.seg_offset), _p(groups.sorted_pos), _p(grad),
+                                 C.byref(_gl(grad_div, grad_group, grad_group_stride, partials, grad_index)),
+                                 _p(P), _p(A), float(lr), float(epsilon), _stream()), "rec_adagrad_rows")
+
+
+def adagrad_dense(p, acc, g, lr, epsilon=1e-6):
+    """paddle.optimizer.Adagrad over a flat buffer (rec_adagrad_dense): p, acc, g contiguous float32 of one length."""
+    for t, n in ((p, "p"), (acc, "acc"), (g, "g")):
+        if not torch.is_tensor(t):
+            raise RecError("%s must be a float32 device tensor" % n)
+        _chk(t, torch.float32, n)
+    if not (p.numel() == acc.numel() == g.numel()):
+        raise RecError("p, acc and g must have one length (%d, %d, %d)" % (p.numel(), acc.numel(), g.numel()))
+    check(lib().rec_adagrad_dense(p.numel(), _p(p), _p(acc), _p(g), float(lr), float(epsilon), _stream()),
+          "rec_adagrad_dense")
 
 
 def _sumsq_ws(ws):

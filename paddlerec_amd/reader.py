@@ -327,6 +327,28 @@ class CriteoTsvReader(_FileBatches):
                          lambda data: parse_criteo_tsv(data, 13, 26, hash_dim, threads, pinned=True), shard)
 
 
+def parse_avazu_csv(data, n_fields=24):
+    """flen/avazu_reader.py:30-49: comma-separated integer lines; a line with any other field count is skipped silently.
+    -> (label [n] i64 = the LAST column, ids [n, n_fields - 1] i64 = the columns in front of it, an empty [n, 0] dense)."""
+    import numpy as np
+    rows = [r for r in (line.strip().split(",") for line in bytes(data).decode().splitlines()) if len(r) == n_fields]
+    arr = np.asarray(rows, dtype=str).astype(np.int64) if rows else np.zeros((0, n_fields), np.int64)
+    t = torch.from_numpy(arr)
+    return t[:, -1].contiguous(), t[:, :-1].contiguous(), torch.zeros(t.shape[0], 0)
+
+
+class AvazuReader(_FileBatches):
+    """flen/avazu_reader.py RecDataset with the batching of the other readers (drop_last, rank sharding of the files):
+    yields (label [B,1], ids [B,23]) on `device`.  Column 0 of ids is in the batch; the net ignores it."""
+
+    def __init__(self, file_list, batch_size, device="cuda", shard=None):
+        super().__init__(file_list, batch_size, device, parse_avazu_csv, shard)
+
+    def _batches(self, files):
+        for label, ids, _ in super()._batches(files):
+            yield label, ids
+
+
 class DinReader:
     """models/rank/din/dinReader.py RecDataset: lines "hist items;hist cats;target item;target cat;label".
     Groups of 20*batch_size samples are sorted by history length (stable) and cut into batches padded to the

@@ -7,6 +7,7 @@ forward and the net-specific middle of `train_step`:
     ... forward, `ids_group` under `with _OnSide(side, cur):` where the net wants it, loss head, backward ...
     self._update_rows(t, lr, cur, side, (groups, grad, grad_div, P, M, V), ...)
     self._finish_step(t, lr, cur, side)
+The two optimizer calls behind them are Adam's; a layer with another rule overrides `_rows_update` / `_dense_update`.
 A layer whose trainer may switch the Adam form declares `lazy_mode = False` on its class; one with a fixed form sets it
 on the instance (paddlerec_amd.trainer probes the class).  The base defines neither.
 """
@@ -126,12 +127,20 @@ class SlotLayerBase:
             self._step_groups = made[0] if len(made) == 1 else made
         return self.step_count, cur, side, self._step_groups
 
+    # -- the optimizer: Adam unless a layer overrides these two (flen.py: Adagrad) ---------------------
+    def _rows_update(self, t, lr, groups, grad, div, P, M, V, **kw):
+        """The update of one table's touched rows: Adam, lazy or every row as self.lazy_mode says."""
+        (self.k.sparse_adam_rows if self.lazy_mode else self.k.adam_rows_all)(groups, grad, div, P, M, V, t, lr, **kw)
+
+    def _dense_update(self, t, lr, p, m, v, g):
+        """The update of the flat dense buffer (or a head of it)."""
+        self.k.adam_dense(p, m, v, g, t, lr)
+
     def _update_rows(self, t, lr, cur, side, *tables, l2=None, **layout):
-        """On the side stream: the hot-row partial sums of every table of the step, then their Adam updates (lazy or
-        every row, as self.lazy_mode says).  tables: (groups, grad, grad_div, P, M, V); layout: grad_group /
-        grad_group_stride of a gradient read in place from a wider row."""
+        """On the side stream: the hot-row partial sums of every table of the step, then their row updates
+        (_rows_update: Adam, lazy or every row as self.lazy_mode says, unless the layer overrides it).  tables: (groups,
+        grad, grad_div, P, M, V); layout: grad_group / grad_group_stride of a gradient read in place from a wider row."""
         k = self.k
-        upd = k.sparse_adam_rows if self.lazy_mode else k.adam_rows_all
         ukw = layout if l2 is None else dict(layout, l2=l2)
         assert len(tables) <= len(_PARTIALS)
         with _OnSide(side, cur):
@@ -142,15 +151,16 @@ class SlotLayerBase:
                 setattr(self, name, pp)
                 pps.append(pp)
             for pp, (groups, grad, div, P, M, V) in zip(pps, tables):
-                upd(groups, grad, div, P, M, V, t, lr, partials=pp, **ukw)
+                self._rows_update(t, lr, groups, grad, div, P, M, V, partials=pp, **ukw)
 
     def _finish_step(self, t, lr, cur, side, n_adam=None):
-        """Dense Adam on the flat buffer (its first n_adam floats), then the side stream joins the current one."""
+        """The dense update (_dense_update: Adam) on the flat buffer (its first n_adam floats), then the side stream joins
+        the current one."""
         d = self.dense
         if n_adam is None:
-            self.k.adam_dense(d.data, d.m, d.v, d.grad, t, lr)
+            self._dense_update(t, lr, d.data, d.m, d.v, d.grad)
         else:
-            self.k.adam_dense(d.data[:n_adam], d.m[:n_adam], d.v[:n_adam], d.grad[:n_adam], t, lr)
+            self._dense_update(t, lr, d.data[:n_adam], d.m[:n_adam], d.v[:n_adam], d.grad[:n_adam])
         if side is not None:
             cur.wait_stream(side)
 

@@ -10,7 +10,7 @@ What differs by construction: a batch never becomes 28 per-sample NumPy arrays (
 [B,26] / [B,13] device tensors), `loss.backward(); optimizer.step()` is the explicit `train_step` chain of the
 host mirrors, and the AUC buckets stay on the device (read back only when a log line prints them).
 
-    python -m paddlerec_amd.trainer -m <config.yaml> [--model deepfm|fm|ffm|deepfefm|fat_deepffm|wide_deep|dnn|dcn|dcn_v2|gatenet|din|xdeepfm|dlrm] [-o runner.epochs=1 ...] [--infer]
+    python -m paddlerec_amd.trainer -m <config.yaml> [--model deepfm|fm|ffm|deepfefm|fat_deepffm|wide_deep|dnn|dcn|dcn_v2|gatenet|flen|din|xdeepfm|dlrm] [-o runner.epochs=1 ...] [--infer]
     python -m torch.distributed.run --nproc-per-node G -m paddlerec_amd.trainer -m <config.yaml>     # collective mode
 """
 import argparse
@@ -24,7 +24,8 @@ from . import checkpoint
 
 logger = logging.getLogger("paddlerec_amd.trainer")
 
-MODELS = ("deepfm", "fm", "ffm", "deepfefm", "fat_deepffm", "wide_deep", "dnn", "dcn", "dcn_v2", "gatenet", "din", "xdeepfm", "dlrm")
+MODELS = ("deepfm", "fm", "ffm", "deepfefm", "fat_deepffm", "wide_deep", "dnn", "dcn", "dcn_v2", "gatenet", "flen", "din",
+          "xdeepfm", "dlrm")
 
 
 # ------------------------------------------------------------------------------------ configuration
@@ -91,6 +92,8 @@ def _dygraph_model(name):
         from .dcn_v2 import DygraphModel
     elif name == "gatenet":
         from .gatenet import DygraphModel
+    elif name == "flen":
+        from .flen import DygraphModel
     elif name == "din":
         from .din import DygraphModel
     elif name == "xdeepfm":
@@ -123,6 +126,8 @@ def create_data_loader(config, model, device, mode="train", shard=None):
     bs = config.get("runner.train_batch_size" if mode == "train" else "runner.infer_batch_size")
     if model == "din":
         return lambda: iter(reader.DinReader(files, bs, device))
+    if model == "flen":
+        return lambda: iter(reader.AvazuReader(files, bs, device, shard=shard))
     return lambda: iter(reader.SlotTextReader(files, bs, device, log1p_dense=(model == "dcn_v2"), shard=shard))
 
 
@@ -250,6 +255,13 @@ def _apply_optimizer_config(config, model, dy_model):
                     "shape=[1]; the GateNet paper has a vector): a lookup is scaled by sigmoid(w_s * sum_k e_k); the table has "
                     "no padding row (id 0 trains); use_embedding_gate=%s, use_hidden_gate=%s",
                     getattr(dy_model, "use_embedding_gate", None), getattr(dy_model, "use_hidden_gate", None))
+    if model == "flen":
+        logger.info("flen: paddle.optimizer.Adagrad (epsilon 1e-6, initial accumulator 1e-3) on every parameter, as the "
+                    "reference's create_optimizer asks (flen/dygraph_model.py:68-72); duplicate rows of the table's "
+                    "gradient are merged first and a zero gradient is an exact no-op, so "
+                    "hyper_parameters.optimizer.lazy_mode is ignored; Dropout(%.2f) after every element of the DNN's "
+                    "layer list and behind fwbi_bn, with the engine's counter-based masks (seed %d)",
+                    getattr(dy_model, "dropout_rate", 0.0), getattr(dy_model, "dropout_seed", 0))
     if model == "dcn_v2":
         logger.info("dcn_v2 train mode: Dropout(%.2f) after every element of the DNN tower (dcn_v2/net.py:181-183) with the "
                     "engine's counter-based masks (seed %d; Paddle's own mask stream is not reproducible), L2Decay(%g) on "
