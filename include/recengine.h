@@ -1563,6 +1563,79 @@ int rec_adagrad_rows(int64_t n_max, int32_t emb_dim, int32_t row_stride, int32_t
                      const rec_grad_layout* grad_layout, float* P, float* A, float lr, float epsilon, void* stream);
 int rec_adagrad_dense(int64_t n, float* p, float* acc, const float* g, float lr, float epsilon, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * AutoFIS (models/rank/autofis/net.py:78-99): the second-order term of AutoDeepFMLayer, fused into the lookup.
+ * ids [batch, num_fields] index the tables V [num_rows, row_stride] (emb_dim floats of a row) and W1 [num_rows, w_stride]
+ * (one float of a row); neither has a padding row; an id outside [0, num_rows) reads as a zero row and raises
+ * REC_FLAG_INDEX_OOB in *status.  The pair list is two HOST int32 arrays cols[num_pairs], rows[num_pairs] with
+ * 0 <= cols[p] < rows[p] < num_fields (checked on every call before any launch), plus plan_dev, the DEVICE copy of what
+ * rec_autofis_plan lays out from the same list (rec_autofis_plan_ints int32s: cols | rows | num_fields + 1 adjacency
+ * offsets | 2 num_pairs adjacency entries, partner + 256 * pair, in pair order).
+ * Limits: 2 <= num_fields <= REC_AUTOFIS_MAX_FIELDS, 1 <= emb_dim <= REC_AUTOFIS_MAX_DIM, 1 <= num_pairs <=
+ * min(REC_AUTOFIS_MAX_PAIRS, num_fields (num_fields - 1) / 2), batch * max(num_fields, num_pairs) < 2^31.
+ *   X0[b]   = [V[ids[b,0]] | .. | V[ids[b,S-1]]]            (stride x0_stride; the rest of a row is not touched)
+ *   L[b,p]  = <V[ids[b,cols[p]]], V[ids[b,rows[p]]]>        (stride l_stride >= num_pairs)
+ *   s[b]    = sum_s W1[ids[b,s]] + sum_p mask[p] * BN_p(L[.,p])[b]
+ * BN_p is Paddle's BatchNorm over the batch (biased variance).  training != 0: batch statistics -> save_mean,
+ * save_invstd [num_pairs]; running = momentum * running + (1 - momentum) * batch; L is written (the backward reads it).
+ * The statistics are (count, mean, M2) partials of fixed sample sets merged with Chan's formula in a fixed order — never
+ * sum x^2 - mean^2.  training == 0: the running statistics, one launch; L is written only if want_L != 0.  The BatchNorm
+ * output is never stored.  Rows of V and X0 that are multiples of 16 bytes move as 16-byte vectors when emb_dim % 4 == 0.
+ * batch == 0 launches nothing.  Fixed summation order: two runs give the same bits.
+ * ---------------------------------------------------------------------------------------- */
+#define REC_AUTOFIS_MAX_FIELDS 64
+#define REC_AUTOFIS_MAX_DIM 64
+#define REC_AUTOFIS_MAX_PAIRS 2016
+int rec_autofis_plan_ints(int32_t num_fields, int32_t num_pairs, size_t* ints);
+/* Host only: validates the pair list and writes its device image into plan (host memory, rec_autofis_plan_ints ints). */
+int rec_autofis_plan(int32_t num_fields, int32_t num_pairs, const int32_t* cols, const int32_t* rows, int32_t* plan);
+int rec_autofis_fwd_workspace_bytes(int64_t batch, int32_t num_fields, int32_t emb_dim, int32_t num_pairs, size_t* bytes);
+int rec_autofis_fwd(int64_t batch, int32_t num_fields, int32_t emb_dim, int32_t row_stride, int32_t w_stride,
+                    int64_t num_rows, const int64_t* ids, const float* V, const float* W1, int32_t num_pairs,
+                    const int32_t* cols, const int32_t* rows, const int32_t* plan_dev, const float* gamma,
+                    const float* beta, const float* mask, float* running_mean, float* running_var, float momentum,
+                    float eps, int32_t training, int32_t want_L, float* X0, int64_t x0_stride, float* L, int64_t l_stride,
+                    float* s, float* save_mean, float* save_invstd, int32_t* status, void* workspace,
+                    size_t workspace_bytes, void* stream);
+int rec_autofis_bwd_workspace_bytes(int64_t batch, int32_t num_fields, int32_t emb_dim, int32_t num_pairs, size_t* bytes);
+/* Backward of the training forward.  dz [batch] = dloss / d s; L, X0, save_mean, save_invstd are the forward's.  With
+ * xhat = (L - mean) * invstd, S0 = sum_b dz[b], S1_p = sum_b dz[b] * xhat[b,p] (summed centred, by row blocks in block
+ * order):
+ *   d_mask[p] = gamma[p] * S1_p + beta[p] * S0;   d_gamma[p] = mask[p] * S1_p;   d_beta[p] = mask[p] * S0
+ *   dL[b,p]   = gamma[p] * invstd[p] * mask[p] * (dz[b] - S0 / batch - xhat[b,p] * S1_p / batch)
+ * and dX [batch, dx_stride] (the layout of X0; on entry the DNN's gradient) gets, IN PLACE, for the fields f of pair p:
+ *   dX[b, cols[p]] += dL[b,p] * X0[b, rows[p]];   dX[b, rows[p]] += dL[b,p] * X0[b, cols[p]]
+ * added per field in pair order.  A field in no pair is not written.  The gradient of a W1 lookup is dz[b]: no kernel.
+ * batch == 0 writes zeros to the three gradients.  dX aliases neither X0 nor L. */
+int rec_autofis_bwd(int64_t batch, int32_t num_fields, int32_t emb_dim, int32_t num_pairs, const int32_t* cols,
+                    const int32_t* rows, const int32_t* plan_dev, const float* dz, const float* L, int64_t l_stride,
+                    const float* X0, int64_t x0_stride, const float* save_mean, const float* save_invstd,
+                    const float* gamma, const float* beta, const float* mask, float* dX, int64_t dx_stride, float* d_mask,
+                    float* d_gamma, float* d_beta, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Linear -> BatchNorm -> ReLU (autofis/net.py:84-88; rec_batchnorm_bwd's relu_mask covers the other order, ReLU -> BN).
+ * rec_batchnorm_relu_fwd: rec_batchnorm_fwd with Y = max(BN(X), 0) written by the apply pass (Y != X).
+ * rec_batchnorm_relu_bwd: dY counts only where Y > 0, in the column sums and in dX; arguments and workspace
+ * (rec_batchnorm_workspace_bytes) as rec_batchnorm_bwd plus Y.
+ * ---------------------------------------------------------------------------------------- */
+int rec_batchnorm_relu_fwd(int64_t m, int32_t n, const float* X, int64_t ldx, const float* gamma, const float* beta,
+                           float* running_mean, float* running_var, float momentum, float eps, int32_t training, float* Y,
+                           int64_t ldy, float* save_mean, float* save_invstd, void* workspace, size_t workspace_bytes,
+                           void* stream);
+int rec_batchnorm_relu_bwd(int64_t m, int32_t n, const float* X, int64_t ldx, const float* Y, int64_t ldy, const float* dY,
+                           int64_t lddy, const float* gamma, const float* save_mean, const float* save_invstd, float* dX,
+                           int64_t lddx, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * SimpleGrda.step() on one parameter (autofis/optimizer.py:39-60), element-wise over n floats:
+ *   acc <- acc + first_iter * p - lr * g;   p <- sign(acc) * max(|acc| - l1_accumulation, 0)
+ * The caller keeps `iterations` and l1_accumulation (host doubles, the reference's expression) and passes
+ * first_iter = max(1 - iterations, 0).  p, acc and g are three buffers.
+ * ---------------------------------------------------------------------------------------- */
+int rec_grda_step(int64_t n, float* p, float* acc, const float* g, float lr, float l1_accumulation, int32_t first_iter,
+                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,7 @@ LIB_PATH = os.path.join(_HERE, "librecengine.so")
 REC_FLAG_INDEX_OOB = 1
 REC_FLAG_EXCHANGE_OVERFLOW = 2
 REC_FLEN_MAX_GROUPS = 8
+REC_AUTOFIS_MAX_FIELDS, REC_AUTOFIS_MAX_DIM, REC_AUTOFIS_MAX_PAIRS = 64, 64, 2016
 
 
 class RecError(RuntimeError):
@@ -240,6 +241,19 @@ SIGNATURES = {
                                _P, _SZ, _P]),
     "rec_adagrad_rows": (C.c_int, [_I64, _I32, _I32, _I32, _P, _P, _P, _P, _P, C.POINTER(GradLayout), _P, _P, _F, _F, _P]),
     "rec_adagrad_dense": (C.c_int, [_I64, _P, _P, _P, _F, _F, _P]),
+    "rec_autofis_plan_ints": (C.c_int, [_I32, _I32, C.POINTER(_SZ)]),
+    "rec_autofis_plan": (C.c_int, [_I32, _I32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "rec_autofis_fwd_workspace_bytes": (C.c_int, [_I64, _I32, _I32, _I32, C.POINTER(_SZ)]),
+    "rec_autofis_fwd": (C.c_int, [_I64, _I32, _I32, _I32, _I32, _I64, _P, _P, _P, _I32, C.POINTER(C.c_int32),
+                                  C.POINTER(C.c_int32), _P, _P, _P, _P, _P, _P, _F, _F, _I32, _I32, _P, _I64, _P, _I64, _P,
+                                  _P, _P, _P, _P, _SZ, _P]),
+    "rec_autofis_bwd_workspace_bytes": (C.c_int, [_I64, _I32, _I32, _I32, C.POINTER(_SZ)]),
+    "rec_autofis_bwd": (C.c_int, [_I64, _I32, _I32, _I32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P, _P, _P, _I64, _P,
+                                  _I64, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _SZ, _P]),
+    "rec_batchnorm_relu_fwd": (C.c_int, [_I64, _I32, _P, _I64, _P, _P, _P, _P, _F, _F, _I32, _P, _I64, _P, _P, _P, _SZ, _P]),
+    "rec_batchnorm_relu_bwd": (C.c_int, [_I64, _I32, _P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _P, _I64, _P, _P, _P, _SZ,
+                                         _P]),
+    "rec_grda_step": (C.c_int, [_I64, _P, _P, _P, _F, _F, _I32, _P]),
     "rec_dense_fold_fwd": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P]),
     "rec_dense_fold_bwd": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _I32, _P]),
     "rec_dense_fold_fwd_full": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P]),

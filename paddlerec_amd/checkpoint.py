@@ -45,6 +45,9 @@ def optimizer_state(net):
         for k in ("m", "v", "m1", "v1"):
             if k in sp:
                 st["sparse." + k] = _np(sp[k])
+    extra = getattr(net, "extra_optimizer_state", None)      # a rule with state of its own (autofis.py: "grda.*")
+    if extra is not None:
+        st.update(extra())
     return st
 
 
@@ -60,6 +63,8 @@ def set_optimizer_state(net, st):
             if "sparse." + k in st and k in net.sparse_state:
                 dst = net.sparse_state[k]
                 dst.copy_(torch.as_tensor(st["sparse." + k]).to(dst.device).reshape(dst.shape))
+    if hasattr(net, "set_extra_optimizer_state"):
+        net.set_extra_optimizer_state(st)
 
 
 def _ps_table(net):

@@ -21,18 +21,20 @@ constexpr int kRowLanes = kBlock / kColTile;
 constexpr int kMaxRowBlocks = 128;
 
 // MODE 0: sum x              MODE 1: sum (x - mean)^2          MODE 2: sum dy, sum dy * (x - mean) * invstd
+// MODE 3: MODE 2 with dy counted only where Y > 0 (Y = relu(BN(X)): Linear -> BN -> ReLU, autofis/net.py:84-88)
 template <int MODE>
 __global__ __launch_bounds__(kBlock) void bn_colreduce_kernel(int64_t M, int N, const float* __restrict__ X, int64_t ldx,
                                                               const float* __restrict__ dY, int64_t lddy,
                                                               const float* __restrict__ mean,
                                                               const float* __restrict__ invstd, float* __restrict__ part0,
-                                                              float* __restrict__ part1) {
+                                                              float* __restrict__ part1,
+                                                              const float* __restrict__ Y = nullptr, int64_t ldy = 0) {
   __shared__ float red[2][kRowLanes][kColTile];
   const int c = blockIdx.x * kColTile + threadIdx.x % kColTile;
   const int rl = threadIdx.x / kColTile;
   const bool on = c < N;
   const float mu = (MODE != 0 && on) ? mean[c] : 0.f;
-  const float is = (MODE == 2 && on) ? invstd[c] : 0.f;
+  const float is = (MODE >= 2 && on) ? invstd[c] : 0.f;
   // rows of this block: a contiguous range (fixed summation order whatever the grid)
   const int64_t per = (M + gridDim.y - 1) / gridDim.y;
   const int64_t r0 = (int64_t)blockIdx.y * per, r1 = r0 + per < M ? r0 + per : M;
@@ -47,13 +49,14 @@ __global__ __launch_bounds__(kBlock) void bn_colreduce_kernel(int64_t M, int N, 
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         x[u] = X[(r + u * kRowLanes) * ldx + c];
-        g[u] = MODE == 2 ? dY[(r + u * kRowLanes) * lddy + c] : 0.f;
+        g[u] = MODE >= 2 ? dY[(r + u * kRowLanes) * lddy + c] : 0.f;
+        if (MODE == 3 && !(Y[(r + u * kRowLanes) * ldy + c] > 0.f)) g[u] = 0.f;
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         if (MODE == 0) p0[u] += x[u];
         if (MODE == 1) { const float d = x[u] - mu; p0[u] += d * d; }
-        if (MODE == 2) { p0[u] += g[u]; p1[u] += g[u] * (x[u] - mu) * is; }
+        if (MODE >= 2) { p0[u] += g[u]; p1[u] += g[u] * (x[u] - mu) * is; }
       }
     }
     for (int u = 0; r < r1; r += kRowLanes, ++u) {
@@ -61,6 +64,11 @@ __global__ __launch_bounds__(kBlock) void bn_colreduce_kernel(int64_t M, int N, 
       if (MODE == 0) p0[u] += x;
       if (MODE == 1) { const float d = x - mu; p0[u] += d * d; }
       if (MODE == 2) { const float g = dY[r * lddy + c]; p0[u] += g; p1[u] += g * (x - mu) * is; }
+      if (MODE == 3) {
+        const float g = Y[r * ldy + c] > 0.f ? dY[r * lddy + c] : 0.f;
+        p0[u] += g;
+        p1[u] += g * (x - mu) * is;
+      }
     }
     a0 = (p0[0] + p0[1]) + (p0[2] + p0[3]);
     a1 = (p1[0] + p1[1]) + (p1[2] + p1[3]);
@@ -73,7 +81,7 @@ __global__ __launch_bounds__(kBlock) void bn_colreduce_kernel(int64_t M, int N, 
 #pragma unroll
     for (int i = 0; i < kRowLanes; ++i) { s0 += red[0][i][threadIdx.x]; s1 += red[1][i][threadIdx.x]; }
     part0[(int64_t)blockIdx.y * N + c] = s0;
-    if (MODE == 2) part1[(int64_t)blockIdx.y * N + c] = s1;
+    if (MODE >= 2) part1[(int64_t)blockIdx.y * N + c] = s1;
   }
 }
 
@@ -100,6 +108,7 @@ __global__ __launch_bounds__(kBlock) void bn_finalize_kernel(int64_t M, int N, i
   if (STEP == 2) { out0[c] = s1; out1[c] = s0; }     // dgamma = sum dy * xhat, dbeta = sum dy
 }
 
+template <bool RELU>
 __global__ __launch_bounds__(kBlock) void bn_apply_kernel(int64_t M, int N, const float* __restrict__ X, int64_t ldx,
                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
                                                           const float* __restrict__ mean, const float* __restrict__ invstd,
@@ -108,7 +117,8 @@ __global__ __launch_bounds__(kBlock) void bn_apply_kernel(int64_t M, int N, cons
   if (i >= M * N) return;
   const int64_t r = i / N;
   const int c = (int)(i - r * N);
-  Y[r * ldy + c] = (X[r * ldx + c] - mean[c]) * invstd[c] * gamma[c] + beta[c];
+  const float y = (X[r * ldx + c] - mean[c]) * invstd[c] * gamma[c] + beta[c];
+  Y[r * ldy + c] = RELU ? fmaxf(y, 0.f) : y;
 }
 
 // dx = gamma * invstd * (dy - sum_dy / M - xhat * sum_dy_xhat / M);  relu_mask: the BN input was a ReLU output — its
@@ -120,7 +130,8 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_apply_kernel(int64_t M, int N, 
                                                               const float* __restrict__ invstd,
                                                               const float* __restrict__ dgamma,
                                                               const float* __restrict__ dbeta, int relu_mask,
-                                                              float* __restrict__ dX, int64_t lddx) {
+                                                              float* __restrict__ dX, int64_t lddx,
+                                                              const float* __restrict__ Y = nullptr, int64_t ldy = 0) {
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= M * N) return;
   const int64_t r = i / N;
@@ -128,7 +139,9 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_apply_kernel(int64_t M, int N, 
   const float x = X[r * ldx + c];
   const float xhat = (x - mean[c]) * invstd[c];
   const float inv_m = 1.f / (float)M;
-  float g = gamma[c] * invstd[c] * (dY[r * lddy + c] - dbeta[c] * inv_m - xhat * dgamma[c] * inv_m);
+  float dy = dY[r * lddy + c];
+  if (Y && !(Y[r * ldy + c] > 0.f)) dy = 0.f;            // rec_batchnorm_relu_bwd: the ReLU BEHIND the BN
+  float g = gamma[c] * invstd[c] * (dy - dbeta[c] * inv_m - xhat * dgamma[c] * inv_m);
   if (relu_mask && !(x > 0.f)) g = 0.f;
   dX[r * lddx + c] = g;
 }
@@ -225,10 +238,11 @@ extern "C" int rec_batchnorm_workspace_bytes(int64_t m, int32_t n, size_t* bytes
   return REC_OK;
 }
 
-extern "C" int rec_batchnorm_fwd(int64_t m, int32_t n, const float* X, int64_t ldx, const float* gamma,
-                                 const float* beta, float* running_mean, float* running_var, float momentum,
-                                 float eps, int32_t training, float* Y, int64_t ldy, float* save_mean,
-                                 float* save_invstd, void* workspace, size_t workspace_bytes, void* stream) {
+template <bool RELU>
+static int batchnorm_fwd_impl(int64_t m, int32_t n, const float* X, int64_t ldx, const float* gamma, const float* beta,
+                              float* running_mean, float* running_var, float momentum, float eps, int32_t training,
+                              float* Y, int64_t ldy, float* save_mean, float* save_invstd, void* workspace,
+                              size_t workspace_bytes, void* stream) {
   REC_REQUIRE(m > 0 && n > 0 && ldx >= n && ldy >= n, REC_EINVAL, "bad sizes");
   REC_REQUIRE(X && gamma && beta && Y && save_mean && save_invstd, REC_EINVAL, "null pointer argument");
   hipStream_t s = (hipStream_t)stream;
@@ -251,21 +265,64 @@ extern "C" int rec_batchnorm_fwd(int64_t m, int32_t n, const float* X, int64_t l
                        part, nullptr);
     hipLaunchKernelGGL(bn_finalize_kernel<1>, dim3(fb), dim3(kBlock), 0, s, m, n, gy, part, nullptr, save_mean,
                        save_invstd, running_mean, running_var, momentum, eps);
-    hipLaunchKernelGGL(bn_apply_kernel, dim3(eb), dim3(kBlock), 0, s, m, n, X, ldx, gamma, beta, save_mean,
+    hipLaunchKernelGGL(bn_apply_kernel<RELU>, dim3(eb), dim3(kBlock), 0, s, m, n, X, ldx, gamma, beta, save_mean,
                        save_invstd, Y, ldy);
   } else {
     REC_REQUIRE(running_mean && running_var, REC_EINVAL, "eval mode needs the running statistics");
     // invstd of the running variance into save_invstd, running mean into save_mean: one tiny launch each way
     hipLaunchKernelGGL(bn_finalize_kernel<1>, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (int64_t)1, n, 1,
                        running_var, nullptr, save_mean, save_invstd, nullptr, nullptr, momentum, eps);
-    hipLaunchKernelGGL(bn_apply_kernel, dim3(eb), dim3(kBlock), 0, s, m, n, X, ldx, gamma, beta, running_mean,
+    hipLaunchKernelGGL(bn_apply_kernel<RELU>, dim3(eb), dim3(kBlock), 0, s, m, n, X, ldx, gamma, beta, running_mean,
                        save_invstd, Y, ldy);
     if (hipMemcpyAsync(save_mean, running_mean, sizeof(float) * n, hipMemcpyDeviceToDevice, s) != hipSuccess) {
       set_error("rec_batchnorm_fwd: copy of the running mean failed");
       return REC_EHIP;
     }
   }
-  return check_launch("rec_batchnorm_fwd");
+  return check_launch(RELU ? "rec_batchnorm_relu_fwd" : "rec_batchnorm_fwd");
+}
+
+extern "C" int rec_batchnorm_fwd(int64_t m, int32_t n, const float* X, int64_t ldx, const float* gamma,
+                                 const float* beta, float* running_mean, float* running_var, float momentum,
+                                 float eps, int32_t training, float* Y, int64_t ldy, float* save_mean,
+                                 float* save_invstd, void* workspace, size_t workspace_bytes, void* stream) {
+  return batchnorm_fwd_impl<false>(m, n, X, ldx, gamma, beta, running_mean, running_var, momentum, eps, training, Y, ldy,
+                                   save_mean, save_invstd, workspace, workspace_bytes, stream);
+}
+
+extern "C" int rec_batchnorm_relu_fwd(int64_t m, int32_t n, const float* X, int64_t ldx, const float* gamma,
+                                      const float* beta, float* running_mean, float* running_var, float momentum,
+                                      float eps, int32_t training, float* Y, int64_t ldy, float* save_mean,
+                                      float* save_invstd, void* workspace, size_t workspace_bytes, void* stream) {
+  REC_REQUIRE(X != Y, REC_EINVAL, "rec_batchnorm_relu_fwd: Y must not be X (the backward reads both)");
+  return batchnorm_fwd_impl<true>(m, n, X, ldx, gamma, beta, running_mean, running_var, momentum, eps, training, Y, ldy,
+                                  save_mean, save_invstd, workspace, workspace_bytes, stream);
+}
+
+extern "C" int rec_batchnorm_relu_bwd(int64_t m, int32_t n, const float* X, int64_t ldx, const float* Y, int64_t ldy,
+                                      const float* dY, int64_t lddy, const float* gamma, const float* save_mean,
+                                      const float* save_invstd, float* dX, int64_t lddx, float* dgamma, float* dbeta,
+                                      void* workspace, size_t workspace_bytes, void* stream) {
+  REC_REQUIRE(m > 0 && n > 0 && ldx >= n && ldy >= n && lddy >= n && lddx >= n, REC_EINVAL, "bad sizes");
+  REC_REQUIRE(X && Y && dY && gamma && save_mean && save_invstd && dX && dgamma && dbeta, REC_EINVAL,
+              "null pointer argument");
+  REC_REQUIRE(dX != X && dX != Y, REC_EINVAL, "rec_batchnorm_relu_bwd: dX must not be X or Y");
+  size_t need = 0;
+  rec_batchnorm_workspace_bytes(m, n, &need);
+  REC_REQUIRE(workspace && workspace_bytes >= need, REC_EWORKSPACE, "workspace too small (%zu < %zu)", workspace_bytes,
+              need);
+  hipStream_t s = (hipStream_t)stream;
+  float* part0 = (float*)workspace;
+  float* part1 = part0 + (size_t)kMaxRowBlocks * n;
+  const int gy = row_blocks(m);
+  hipLaunchKernelGGL(bn_colreduce_kernel<3>, dim3((n + kColTile - 1) / kColTile, gy), dim3(kBlock), 0, s, m, n, X, ldx,
+                     dY, lddy, save_mean, save_invstd, part0, part1, Y, ldy);
+  hipLaunchKernelGGL(bn_finalize_kernel<2>, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, m, n, gy, part0, part1,
+                     dgamma, dbeta, nullptr, nullptr, 0.f, 0.f);
+  const int64_t total = m * n;
+  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, m, n, X,
+                     ldx, dY, lddy, gamma, save_mean, save_invstd, dgamma, dbeta, 0, dX, lddx, Y, ldy);
+  return check_launch("rec_batchnorm_relu_bwd");
 }
 
 extern "C" int rec_batchnorm_bwd(int64_t m, int32_t n, const float* X, int64_t ldx, const float* dY, int64_t lddy,

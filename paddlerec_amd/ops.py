@@ -824,6 +824,205 @@ def flen_bwd(ids, num_rows, group_begin, kernel_mf, FW, dH, g, ws, status=None, 
     return g, out, status
 
 
+# ------------------------------------------------------------------ AutoFIS gated pair term (rank/autofis)
+class AutofisPairs:
+    """A pair list of AutoFIS, checked once: cols / rows (host int32 arrays, 0 <= cols[p] < rows[p] < num_fields) and the
+    device image rec_autofis_plan lays out from them (cols | rows | the per-field adjacency of the backward)."""
+
+    def __init__(self, cols, rows, num_fields, device):
+        try:
+            c, r = [int(x) for x in cols], [int(x) for x in rows]
+        except TypeError:
+            raise RecError("autofis: cols and rows must be sequences of ints")
+        S, P = int(num_fields), len(c)
+        if len(r) != P:
+            raise RecError("autofis: cols and rows must have one length (%d, %d)" % (P, len(r)))
+        if not 2 <= S <= _lib.REC_AUTOFIS_MAX_FIELDS:
+            raise RecError("autofis: num_fields %d must be 2 .. %d" % (S, _lib.REC_AUTOFIS_MAX_FIELDS))
+        if not 1 <= P <= min(_lib.REC_AUTOFIS_MAX_PAIRS, S * (S - 1) // 2):
+            raise RecError("autofis: %d pairs; must be 1 .. min(%d, num_fields (num_fields - 1) / 2 = %d)"
+                           % (P, _lib.REC_AUTOFIS_MAX_PAIRS, S * (S - 1) // 2))
+        for p, (a, b) in enumerate(zip(c, r)):
+            if not 0 <= a < b < S:
+                raise RecError("autofis: pair %d = (%d, %d) must satisfy 0 <= col < row < num_fields = %d" % (p, a, b, S))
+        self.num_fields, self.n = S, P
+        self.cols, self.rows = (C.c_int32 * P)(*c), (C.c_int32 * P)(*r)
+        n = C.c_size_t(0)
+        check(lib().rec_autofis_plan_ints(S, P, C.byref(n)), "rec_autofis_plan_ints")
+        host = (C.c_int32 * n.value)()
+        check(lib().rec_autofis_plan(S, P, self.cols, self.rows, host), "rec_autofis_plan")
+        self.plan = torch.tensor(list(host), dtype=torch.int32, device=device)
+
+
+def _autofis_args(pairs, gamma, beta, mask, what):
+    if not isinstance(pairs, AutofisPairs):
+        raise RecError("%s: pairs must be an ops.AutofisPairs" % what)
+    P = pairs.n
+    for t, nm in ((gamma, "gamma"), (beta, "beta"), (mask, "mask")):
+        if not torch.is_tensor(t):
+            raise RecError("%s: %s must be a float32 device tensor" % (what, nm))
+        _chk(t, torch.float32, nm)
+        if t.numel() != P:
+            raise RecError("%s: %s must hold P = %d floats" % (what, nm, P))
+    return P
+
+
+def autofis_fwd(ids, V, W1, pairs, gamma, beta, mask, running_mean, running_var, ws, training=True, momentum=0.9,
+                eps=1e-5, want_L=False, status=None, out=None):
+    """Lookup + gated, batch-normalised pair term in one pass (rec_autofis_fwd): ids [B,S] i64, V [N,D] and W1 [N] or
+    [N,1] (rows may be strided), pairs an AutofisPairs, gamma / beta / mask [P] and the running statistics [P] of the pair
+    BatchNorm -> (X0 [B, S*D], s [B] = sum_s W1[ids] + sum_p mask_p BN_p(L)[b], L [B,P] or None, save_mean, save_invstd
+    (None in eval mode), status).  training: batch statistics, the running ones move, L is written; eval: the running
+    statistics, L only with want_L.  out = (X0, L): column blocks of wider buffers are fine (unit column stride)."""
+    P = _autofis_args(pairs, gamma, beta, mask, "autofis_fwd")
+    _chk(ids, torch.int64, "ids")
+    if ids.dim() != 2 or ids.shape[1] != pairs.num_fields:
+        raise RecError("autofis_fwd: ids must be [B, S = %d]" % pairs.num_fields)
+    B, S = ids.shape
+    _, v_stride = _chk_table(V, "V")
+    if V.dim() != 2 or not 1 <= V.shape[1] <= _lib.REC_AUTOFIS_MAX_DIM:
+        raise RecError("autofis_fwd: V must be [N, D] with 1 <= D <= %d" % _lib.REC_AUTOFIS_MAX_DIM)
+    N, D = V.shape
+    w_dim, w_stride = _chk_table(W1, "W1")
+    if w_dim != 1 or W1.shape[0] != N:
+        raise RecError("autofis_fwd: W1 must be [N] or [N, 1] with the rows of V")
+    for t, nm in ((running_mean, "running_mean"), (running_var, "running_var")):
+        _chk(t, torch.float32, nm, (P,))
+    dev = ids.device
+    X0, L = out if out is not None else (None, None)
+    if X0 is None:
+        X0 = torch.empty(B, S * D, dtype=torch.float32, device=dev)
+    writes_L = bool(training) or bool(want_L)
+    if L is None and writes_L:
+        L = torch.empty(B, P, dtype=torch.float32, device=dev)
+    ld_x = _dcn_rows(X0, B, S * D, "X0")
+    ld_l = _dcn_rows(L, B, P, "L") if writes_L else 0
+    if writes_L and _overlap(X0, L):
+        raise RecError("autofis_fwd: X0 and L must not overlap")
+    s = torch.empty(B, dtype=torch.float32, device=dev)
+    sm = si = None
+    if training:
+        sm = torch.empty(P, dtype=torch.float32, device=dev)
+        si = torch.empty(P, dtype=torch.float32, device=dev)
+    if status is None:
+        status = new_status(dev)
+    nbytes = C.c_size_t(0)
+    check(lib().rec_autofis_fwd_workspace_bytes(B, S, D, P, C.byref(nbytes)), "rec_autofis_fwd_workspace_bytes")
+    wk = ws.get(nbytes.value)
+    check(lib().rec_autofis_fwd(B, S, D, v_stride, w_stride, N, _p(ids), _p(V), _p(W1), P, pairs.cols, pairs.rows,
+                                _p(pairs.plan), _p(gamma), _p(beta), _p(mask), _p(running_mean), _p(running_var),
+                                float(momentum), float(eps), int(bool(training)), int(bool(want_L)), _p(X0), ld_x,
+                                _p(L if writes_L else None), ld_l, _p(s), _p(sm), _p(si), _p(status), _p(wk),
+                                C.c_size_t(wk.numel()), _stream()), "rec_autofis_fwd")
+    return X0, s, (L if writes_L else None), sm, si, status
+
+
+def autofis_bwd(dz, L, X0, pairs, save_mean, save_invstd, gamma, beta, mask, dX, ws, out=None):
+    """Backward of the training autofis_fwd (rec_autofis_bwd): dz [B] or [B,1] = dloss / d s; dX [B, S*D] (a view as X0)
+    holds the DNN's layer-0 gradient on entry and gets the pair term's gradient ADDED in place (a field in no pair is not
+    written).  -> (dX, d_mask [P], d_gamma [P], d_beta [P]); out = the three gradients.  Fixed-order sums."""
+    P = _autofis_args(pairs, gamma, beta, mask, "autofis_bwd")
+    S = pairs.num_fields
+    if not torch.is_tensor(dz):
+        raise RecError("autofis_bwd: dz must be a float32 device tensor")
+    _chk(dz, torch.float32, "dz")
+    B = dz.numel()
+    if not torch.is_tensor(X0) or X0.dim() != 2 or X0.shape[1] % S:
+        raise RecError("autofis_bwd: X0 must be a float32 device matrix [B, S * D]")
+    D = X0.shape[1] // S
+    if not 1 <= D <= _lib.REC_AUTOFIS_MAX_DIM:
+        raise RecError("autofis_bwd: D = %d must be 1 .. %d" % (D, _lib.REC_AUTOFIS_MAX_DIM))
+    ld_x, ld_l, ld_dx = _dcn_rows(X0, B, S * D, "X0"), _dcn_rows(L, B, P, "L"), _dcn_rows(dX, B, S * D, "dX")
+    if _overlap(dX, X0) or _overlap(dX, L):
+        raise RecError("autofis_bwd: dX must not overlap X0 or L")
+    for t, nm in ((save_mean, "save_mean"), (save_invstd, "save_invstd")):
+        _chk(t, torch.float32, nm, (P,))
+    dev = dz.device
+    d_mask, d_gamma, d_beta = out if out is not None else (None, None, None)
+    made = []
+    for t, nm in ((d_mask, "d_mask"), (d_gamma, "d_gamma"), (d_beta, "d_beta")):
+        if t is None:
+            t = torch.empty(P, dtype=torch.float32, device=dev)
+        _chk(t, torch.float32, nm)
+        if t.numel() != P:
+            raise RecError("autofis_bwd: %s must hold P = %d floats" % (nm, P))
+        made.append(t)
+    d_mask, d_gamma, d_beta = made
+    nbytes = C.c_size_t(0)
+    check(lib().rec_autofis_bwd_workspace_bytes(B, S, D, P, C.byref(nbytes)), "rec_autofis_bwd_workspace_bytes")
+    wk = ws.get(nbytes.value)
+    check(lib().rec_autofis_bwd(B, S, D, P, pairs.cols, pairs.rows, _p(pairs.plan), _p(dz), _p(L), ld_l, _p(X0), ld_x,
+                                _p(save_mean), _p(save_invstd), _p(gamma), _p(beta), _p(mask), _p(dX), ld_dx, _p(d_mask),
+                                _p(d_gamma), _p(d_beta), _p(wk), C.c_size_t(wk.numel()), _stream()), "rec_autofis_bwd")
+    return dX, d_mask, d_gamma, d_beta
+
+
+def batchnorm_relu_fwd(X, gamma, beta, running_mean, running_var, ws, training=True, momentum=0.9, eps=1e-5, out=None):
+    """relu(BatchNorm(X)) for Linear -> BN -> ReLU (autofis/net.py:84-88): batchnorm_fwd with the ReLU in its apply pass.
+    -> (Y, save_mean, save_invstd).  Y is not X: batchnorm_relu_bwd reads both."""
+    ldx = _chk_mat(X, "X")
+    m, n = X.shape
+    for t, nm in ((gamma, "gamma"), (beta, "beta"), (running_mean, "running_mean"), (running_var, "running_var")):
+        _chk(t, torch.float32, nm, (n,))
+    if out is None:
+        out = torch.empty(m, n, dtype=torch.float32, device=X.device)
+    ldy = _chk_mat(out, "out")
+    if tuple(out.shape) != (m, n) or _overlap(out, X):
+        raise RecError("batchnorm_relu_fwd: out must be [m, n] and must not overlap X")
+    sm = torch.empty(n, dtype=torch.float32, device=X.device)
+    si = torch.empty(n, dtype=torch.float32, device=X.device)
+    nbytes = C.c_size_t(0)
+    check(lib().rec_batchnorm_workspace_bytes(m, n, C.byref(nbytes)))
+    w = ws.get(nbytes.value)
+    check(lib().rec_batchnorm_relu_fwd(m, n, _p(X), ldx, _p(gamma), _p(beta), _p(running_mean), _p(running_var),
+                                       float(momentum), float(eps), int(bool(training)), _p(out), ldy, _p(sm), _p(si),
+                                       _p(w), C.c_size_t(w.numel()), _stream()), "rec_batchnorm_relu_fwd")
+    return out, sm, si
+
+
+def batchnorm_relu_bwd(X, Y, dY, gamma, save_mean, save_invstd, ws, dgamma=None, dbeta=None, out=None):
+    """Backward of batchnorm_relu_fwd: dY counts only where Y > 0, in the column sums and in dX.
+    -> (dX, dgamma, dbeta)."""
+    ldx, ldy, lddy = _chk_mat(X, "X"), _chk_mat(Y, "Y"), _chk_mat(dY, "dY")
+    m, n = X.shape
+    if tuple(Y.shape) != (m, n) or tuple(dY.shape) != (m, n):
+        raise RecError("batchnorm_relu_bwd: X, Y and dY must have one shape")
+    dev = X.device
+    if out is None:
+        out = torch.empty(m, n, dtype=torch.float32, device=dev)
+    if tuple(out.shape) != (m, n) or _overlap(out, X) or _overlap(out, Y):
+        raise RecError("batchnorm_relu_bwd: dX must be [m, n] and must not overlap X or Y")
+    if dgamma is None:
+        dgamma = torch.empty(n, dtype=torch.float32, device=dev)
+    if dbeta is None:
+        dbeta = torch.empty(n, dtype=torch.float32, device=dev)
+    for t, nm in ((gamma, "gamma"), (save_mean, "save_mean"), (save_invstd, "save_invstd"), (dgamma, "dgamma"),
+                  (dbeta, "dbeta")):
+        _chk(t, torch.float32, nm, (n,))
+    nbytes = C.c_size_t(0)
+    check(lib().rec_batchnorm_workspace_bytes(m, n, C.byref(nbytes)))
+    w = ws.get(nbytes.value)
+    check(lib().rec_batchnorm_relu_bwd(m, n, _p(X), ldx, _p(Y), ldy, _p(dY), lddy, _p(gamma), _p(save_mean),
+                                       _p(save_invstd), _p(out), _chk_mat(out, "dX"), _p(dgamma), _p(dbeta), _p(w),
+                                       C.c_size_t(w.numel()), _stream()), "rec_batchnorm_relu_bwd")
+    return out, dgamma, dbeta
+
+
+def grda_step(p, acc, g, lr, l1_accumulation, first_iter):
+    """SimpleGrda.step() on one parameter (rec_grda_step): acc += first_iter * p - lr * g; p = sign(acc) * max(|acc| -
+    l1_accumulation, 0).  p, acc, g contiguous float32 of one length; the caller keeps iterations and l1_accumulation."""
+    for t, n in ((p, "p"), (acc, "acc"), (g, "g")):
+        if not torch.is_tensor(t):
+            raise RecError("%s must be a float32 device tensor" % n)
+        _chk(t, torch.float32, n)
+    if not (p.numel() == acc.numel() == g.numel()):
+        raise RecError("p, acc and g must have one length (%d, %d, %d)" % (p.numel(), acc.numel(), g.numel()))
+    if first_iter not in (0, 1) or not float(l1_accumulation) >= 0.0:
+        raise RecError("grda_step: first_iter must be 0 or 1 and l1_accumulation >= 0")
+    check(lib().rec_grda_step(p.numel(), _p(p), _p(acc), _p(g), float(lr), float(l1_accumulation), int(first_iter),
+                              _stream()), "rec_grda_step")
+
+
 # ------------------------------------------------------------------ GateNet gates (rank/gatenet)
 def _gate_emb_args(ids, W, gate_w, what):
     """Checks shared by gate_emb_fwd / gate_emb_bwd -> (B, S, D, table row stride, N)."""

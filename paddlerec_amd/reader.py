@@ -349,6 +349,39 @@ class AvazuReader(_FileBatches):
             yield label, ids
 
 
+class AutofisReader:
+    """autofis/criteo_reader.py RecDataset: the data directory holds two whitespace-separated text files, `*x.txt` with
+    S int64 ids per line and `*y.txt` with one label per line.  Yields (label [B,1], ids [B,S]) on `device` with the
+    batching of the other readers (drop_last); len() is the number of batches (the trainer's lr decay needs it).  shard =
+    (rank, world): every rank takes its contiguous block of the samples."""
+
+    def __init__(self, file_list, batch_size, device="cuda", shard=None):
+        self.file_list, self.batch_size, self.device = list(file_list), int(batch_size), device
+        x = y = None
+        for path in self.file_list:                                      # criteo_reader.py:24-28
+            if path.endswith("x.txt"):
+                x = np.loadtxt(path, dtype=np.int64, ndmin=2)
+            elif path.endswith("y.txt"):
+                y = np.loadtxt(path, dtype=np.int64, ndmin=1)
+        if x is None or y is None:
+            raise ValueError("autofis needs a *x.txt and a *y.txt file, got %s" % [os.path.basename(f) for f in file_list])
+        if len(x) != len(y):
+            raise ValueError("%d lines of ids against %d labels" % (len(x), len(y)))
+        if shard is not None:
+            rank, world = shard
+            blk = len(x) // world
+            x, y = x[rank * blk:(rank + 1) * blk], y[rank * blk:(rank + 1) * blk]
+        self.x, self.y = torch.from_numpy(np.ascontiguousarray(x)), torch.from_numpy(np.ascontiguousarray(y)).reshape(-1, 1)
+
+    def __len__(self):
+        return len(self.x) // self.batch_size
+
+    def __iter__(self):
+        B = self.batch_size
+        for i in range(len(self)):
+            yield self.y[i * B:(i + 1) * B].to(self.device), self.x[i * B:(i + 1) * B].to(self.device)
+
+
 class DinReader:
     """models/rank/din/dinReader.py RecDataset: lines "hist items;hist cats;target item;target cat;label".
     Groups of 20*batch_size samples are sorted by history length (stable) and cut into batches padded to the

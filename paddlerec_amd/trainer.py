@@ -10,7 +10,7 @@ What differs by construction: a batch never becomes 28 per-sample NumPy arrays (
 [B,26] / [B,13] device tensors), `loss.backward(); optimizer.step()` is the explicit `train_step` chain of the
 host mirrors, and the AUC buckets stay on the device (read back only when a log line prints them).
 
-    python -m paddlerec_amd.trainer -m <config.yaml> [--model deepfm|fm|ffm|deepfefm|fat_deepffm|wide_deep|dnn|dcn|dcn_v2|gatenet|flen|din|xdeepfm|dlrm] [-o runner.epochs=1 ...] [--infer]
+    python -m paddlerec_amd.trainer -m <config.yaml> [--model deepfm|fm|ffm|deepfefm|fat_deepffm|wide_deep|dnn|dcn|dcn_v2|gatenet|flen|autofis|din|xdeepfm|dlrm] [-o runner.epochs=1 ...] [--infer]
     python -m torch.distributed.run --nproc-per-node G -m paddlerec_amd.trainer -m <config.yaml>     # collective mode
 """
 import argparse
@@ -24,8 +24,8 @@ from . import checkpoint
 
 logger = logging.getLogger("paddlerec_amd.trainer")
 
-MODELS = ("deepfm", "fm", "ffm", "deepfefm", "fat_deepffm", "wide_deep", "dnn", "dcn", "dcn_v2", "gatenet", "flen", "din",
-          "xdeepfm", "dlrm")
+MODELS = ("deepfm", "fm", "ffm", "deepfefm", "fat_deepffm", "wide_deep", "dnn", "dcn", "dcn_v2", "gatenet", "flen", "autofis",
+          "din", "xdeepfm", "dlrm")
 
 
 # ------------------------------------------------------------------------------------ configuration
@@ -94,6 +94,8 @@ def _dygraph_model(name):
         from .gatenet import DygraphModel
     elif name == "flen":
         from .flen import DygraphModel
+    elif name == "autofis":
+        from .autofis import DygraphModel
     elif name == "din":
         from .din import DygraphModel
     elif name == "xdeepfm":
@@ -128,6 +130,11 @@ def create_data_loader(config, model, device, mode="train", shard=None):
         return lambda: iter(reader.DinReader(files, bs, device))
     if model == "flen":
         return lambda: iter(reader.AvazuReader(files, bs, device, shard=shard))
+    if model == "autofis":
+        rd = reader.AutofisReader(files, bs, device, shard=shard)
+        loader = lambda: iter(rd)
+        loader.num_batches = len(rd)                  # len(train_dataloader) of autofis/trainer.py:107
+        return loader
     return lambda: iter(reader.SlotTextReader(files, bs, device, log1p_dense=(model == "dcn_v2"), shard=shard))
 
 
@@ -262,6 +269,16 @@ def _apply_optimizer_config(config, model, dy_model):
                     "hyper_parameters.optimizer.lazy_mode is ignored; Dropout(%.2f) after every element of the DNN's "
                     "layer list and behind fwbi_bn, with the engine's counter-based masks (seed %d)",
                     getattr(dy_model, "dropout_rate", 0.0), getattr(dy_model, "dropout_seed", 0))
+    if model == "autofis":
+        logger.info("autofis: stage %d with %d field pairs%s; both tables are plain nn.Embedding (dense gradient, no "
+                    "padding row), so Adam is the non-lazy form and every row moves every step "
+                    "(hyper_parameters.optimizer.lazy_mode is ignored); the learning rate is multiplied by "
+                    "hyper_parameters.optimizer.gamma before batch b whenever (b + 1) %% (batches per epoch // 5) == 0 and "
+                    "carries across epochs (autofis/trainer.py:106-116)", dy_model.stage, dy_model.num_pairs,
+                    " — SimpleGrda(lr 1, c %g, mu %g; accumulator drawn from U(-0.1, 0.1)) on `mask`, Adam on everything "
+                    "else, and comb_mask.npy = (mask != 0) is written after the last epoch" % (dy_model.grad_c,
+                                                                                              dy_model.grad_mu)
+                    if dy_model.stage == 0 else " kept by comb_mask — Adam on everything, `mask` included")
     if model == "dcn_v2":
         logger.info("dcn_v2 train mode: Dropout(%.2f) after every element of the DNN tower (dcn_v2/net.py:181-183) with the "
                     "engine's counter-based masks (seed %d; Paddle's own mask stream is not reproducible), L2Decay(%g) on "
@@ -306,6 +323,11 @@ def train(config, model, device="cuda", kernels=None, comm=None):
                          "of every rank's file split!")
     summaries = []
     pending_iter = None
+    decay = None
+    if model == "autofis":                            # the step decay of its own trainer (autofis/trainer.py:106-116)
+        from .autofis import StepDecay
+        decay = StepDecay(config.get("hyper_parameters.optimizer.learning_rate", 0.001),
+                          config.get("hyper_parameters.optimizer.gamma", 0.7), loader.num_batches)
     for epoch_id in range(config.get("last_epoch", -1) + 1, epochs):
         metric_list, metric_names = dy_model_class.create_metrics(dy_model.device)
         epoch_begin = time.time()
@@ -319,6 +341,8 @@ def train(config, model, device="cuda", kernels=None, comm=None):
             reader_cost += time.time() - reader_start
             reader_total += time.time() - reader_start
             t0 = time.time()
+            if decay is not None:
+                dy_model.lr = decay.before_batch(batch_id)
             fkw = {"next_batch": nxt} if world > 1 else {}
             loss, metric_list, _ = dy_model_class.train_forward(dy_model, metric_list, batch, config, **fkw)
             run_cost += time.time() - t0
@@ -366,6 +390,12 @@ def train(config, model, device="cuda", kernels=None, comm=None):
         logger.info("epoch: %d done, %s epoch time: %.2f s", epoch_id,
                     "".join("%s: %.6f," % kv for kv in vals.items()), elapsed)
         summaries.append(s)
+    if model == "autofis" and dy_model.stage == 0:    # autofis/trainer.py:219-222, into the working directory
+        import numpy as np
+        path = config.get("runner.comb_mask_path") or "comb_mask.npy"
+        np.save(path, dy_model.comb_mask_of_mask())
+        logger.info("autofis: stage 0 kept %d of %d pairs; wrote %s", int(dy_model.comb_mask_of_mask().sum()),
+                    dy_model.num_pairs, path)
     return summaries, dy_model
 
 
