@@ -1636,6 +1636,67 @@ int rec_batchnorm_relu_bwd(int64_t m, int32_t n, const float* X, int64_t ldx, co
 int rec_grda_step(int64_t n, float* p, float* acc, const float* g, float lr, float l1_accumulation, int32_t first_iter,
                   void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * DIEN (models/rank/dien/net.py) — csrc/dien_ops.hip.  Every sum has a fixed order: reruns are bit-identical.
+ *
+ * GRU recurrence, ONE launch for the whole time loop of one layer (paddle.nn.GRU / GRUCell [EXT], gate order r, z, c):
+ *   r = sigmoid(Gi_r + W_hr h + b_hr)   z = sigmoid(Gi_z + W_hz h + b_hz)
+ *   c = tanh(Gi_c + r * (W_hc h + b_hc))   h' = z * h + (1 - z) * c,   h_0 = 0
+ * Gi [batch, steps, 3*hidden] = X W_ih^T + b_ih is the caller's GEMM (rec_gemm_f32 over batch*steps rows); W_hh
+ * [3*hidden, hidden] row-major, 16-byte aligned; hidden a multiple of 4, <= 256.  The products h W_hh^T run on
+ * v_mfma_f32_16x16x4_f32 (exact f32, k-ordered).
+ * rec_gru_seq_fwd: H_out [batch, steps, hidden]; saved (nullable: inference) [batch, steps, 5*hidden] = r | z | c | hc
+ *   | hp with hc = W_hc h + b_hc and hp = h_{t-1}.
+ * rec_gru_seq_bwd: walks t = steps-1 .. 0 from dH_out [batch, steps, hidden] (a gradient per step) and / or dh_T
+ *   [batch, hidden] (a gradient of the last state); both nullable.  Writes dGi and dGh [batch, steps, 3*hidden] (they
+ *   differ in the c columns, by r) and carries dh_{t-1} = dGh_t W_hh + dh_t * z_t.  The weight gradients and dX are the
+ *   caller's GEMMs over batch*steps rows: dW_ih = dGi^T X, db_ih = colsum(dGi), dW_hh = dGh^T H_prev, db_hh =
+ *   colsum(dGh), dX = dGi W_ih (H_prev = the hp columns of saved, row stride 5*hidden).
+ * ---------------------------------------------------------------------------------------- */
+int rec_gru_seq_fwd(int64_t batch, int32_t steps, int32_t hidden, const float* Gi, const float* W_hh, const float* b_hh,
+                    float* H_out, float* saved, void* stream);
+int rec_gru_seq_bwd(int64_t batch, int32_t steps, int32_t hidden, const float* saved, const float* W_hh,
+                    const float* dH_out, const float* dh_T, float* dGi, float* dGh, void* stream);
+
+/* DIEN's auxiliary loss (net.py:219-254), kept as written: for t = 0 .. steps-2
+ *   p = gru_out[b,t] . hist[b,t+1];   n = clip(gru_out[b,t] . neg[b,t+1], -15, 15)
+ *   aux[0] = (1 / batch) sum_b sum_t log(1e-8 + sigmoid(p)) + log(1e-8 + sigmoid(n))
+ * gru_out, hist [batch, steps, item_dim + cat_dim] (hist: the gathered rows); neg[b,t] = [W_neg_item[neg_item[b,t]] |
+ * W_neg_cat[neg_cat[b,t]]], where the id padding_idx (< 0: none) reads as zeros and an id outside its table reads as
+ * zeros and raises REC_FLAG_INDEX_OOB.  workspace >= rec_dien_aux_workspace_bytes.
+ * rec_dien_aux_bwd, d_aux = dloss / d aux: d_gru_out [batch, steps, H] (zero at t = steps-1), d_hist[b,t+1] (+)=
+ * dp gru_out[b,t] (accumulate_hist 0: written, zero at t = 0), d_neg [batch, steps, H] = the gradient of the
+ * concatenated neg rows (zero at t = 0 and where |n| >= 15). */
+int rec_dien_aux_workspace_bytes(int64_t batch, int32_t steps, size_t* bytes);
+int rec_dien_aux_fwd(int64_t batch, int32_t steps, int32_t item_dim, int32_t cat_dim, const float* gru_out,
+                     const float* hist, const int64_t* neg_item, const int64_t* neg_cat, const float* W_neg_item,
+                     int32_t item_stride, int64_t item_rows, const float* W_neg_cat, int32_t cat_stride, int64_t cat_rows,
+                     int64_t padding_idx, float* aux, int32_t* status, void* workspace, size_t workspace_bytes,
+                     void* stream);
+int rec_dien_aux_bwd(int64_t batch, int32_t steps, int32_t item_dim, int32_t cat_dim, const float* gru_out,
+                     const float* hist, const int64_t* neg_item, const int64_t* neg_cat, const float* W_neg_item,
+                     int32_t item_stride, int64_t item_rows, const float* W_neg_cat, int32_t cat_stride, int64_t cat_rows,
+                     int64_t padding_idx, float d_aux, float* d_gru_out, float* d_hist, int32_t accumulate_hist,
+                     float* d_neg, int32_t* status, void* stream);
+
+/* DIEN's attention over positions (net.py:192-209), composed around the caller's GEMMs of the attention MLP:
+ * rec_dien_att_feat_fwd: feat [n, 4*emb_dim] = [h, q, h - q, h * q] of hist, q [n, emb_dim] (n = batch * steps).
+ * rec_dien_att_feat_bwd: d_hist (+)= d0 + d2 + d3 * q;  d_q = d1 - d2 + d3 * h  for dfeat = [d0, d1, d2, d3].
+ * rec_dien_attention_seq_fwd: w [batch, steps] = softmax_t((score + mask) * scale), x_att [batch, steps, emb_dim] =
+ *   w[b,t] * hist[b,t,:] (not pooled).  mask is additive f32 (0 / -1e9); a row masked everywhere comes out uniform by
+ *   plain arithmetic.
+ * rec_dien_attention_seq_bwd: from dx_att [batch, steps, emb_dim], g_t = dx_att_t . hist_t:
+ *   dscore [batch, steps] = scale * w_t (g_t - sum_s w_s g_s)  (the gradient of the MLP's output),
+ *   d_hist[b,t,:] (+)= w_t dx_att[b,t,:]. */
+int rec_dien_att_feat_fwd(int64_t n, int32_t emb_dim, const float* hist, const float* q, float* feat, void* stream);
+int rec_dien_att_feat_bwd(int64_t n, int32_t emb_dim, const float* hist, const float* q, const float* dfeat, float* d_hist,
+                          int32_t accumulate_hist, float* d_q, void* stream);
+int rec_dien_attention_seq_fwd(int64_t batch, int32_t steps, int32_t emb_dim, const float* score, const float* mask,
+                               const float* hist, float scale, float* w, float* x_att, void* stream);
+int rec_dien_attention_seq_bwd(int64_t batch, int32_t steps, int32_t emb_dim, const float* w, const float* hist,
+                               const float* dx_att, float scale, float* dscore, float* d_hist, int32_t accumulate_hist,
+                               void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -254,6 +254,17 @@ SIGNATURES = {
     "rec_batchnorm_relu_bwd": (C.c_int, [_I64, _I32, _P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _P, _I64, _P, _P, _P, _SZ,
                                          _P]),
     "rec_grda_step": (C.c_int, [_I64, _P, _P, _P, _F, _F, _I32, _P]),
+    "rec_gru_seq_fwd": (C.c_int, [_I64, _I32, _I32, _P, _P, _P, _P, _P, _P]),
+    "rec_gru_seq_bwd": (C.c_int, [_I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
+    "rec_dien_aux_workspace_bytes": (C.c_int, [_I64, _I32, C.POINTER(_SZ)]),
+    "rec_dien_aux_fwd": (C.c_int, [_I64, _I32, _I32, _I32, _P, _P, _P, _P, _P, _I32, _I64, _P, _I32, _I64, _I64, _P, _P, _P,
+                                   _SZ, _P]),
+    "rec_dien_aux_bwd": (C.c_int, [_I64, _I32, _I32, _I32, _P, _P, _P, _P, _P, _I32, _I64, _P, _I32, _I64, _I64, _F, _P, _P,
+                                   _I32, _P, _P, _P]),
+    "rec_dien_att_feat_fwd": (C.c_int, [_I64, _I32, _P, _P, _P, _P]),
+    "rec_dien_att_feat_bwd": (C.c_int, [_I64, _I32, _P, _P, _P, _P, _I32, _P, _P]),
+    "rec_dien_attention_seq_fwd": (C.c_int, [_I64, _I32, _I32, _P, _P, _P, _F, _P, _P, _P]),
+    "rec_dien_attention_seq_bwd": (C.c_int, [_I64, _I32, _I32, _P, _P, _P, _F, _P, _P, _I32, _P]),
     "rec_dense_fold_fwd": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P]),
     "rec_dense_fold_bwd": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _I32, _P]),
     "rec_dense_fold_fwd_full": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P]),

@@ -1838,6 +1838,206 @@ def din_attention_pool_bwd(hist_item, hist_cat, tgt_item_seq, tgt_cat_seq, w_his
     return dh, dq
 
 
+# ------------------------------------------------------------------ DIEN (rank/dien): GRU recurrence, aux loss, attention
+GRU_MAX_HIDDEN = 256
+
+
+def _gru_dims(t, cols, name):
+    """t [B, T, cols * H] contiguous f32 -> (B, T, H)."""
+    _chk(t, torch.float32, name)
+    if t.dim() != 3 or t.shape[2] % cols or t.shape[1] < 1:
+        raise RecError("%s must be [B, T, %d * H] with T >= 1" % (name, cols))
+    B, T, H = t.shape[0], t.shape[1], t.shape[2] // cols
+    if H % 4 or not 0 < H <= GRU_MAX_HIDDEN:
+        raise RecError("%s: hidden size %d unsupported (a multiple of 4, at most %d)" % (name, H, GRU_MAX_HIDDEN))
+    return B, T, H
+
+
+def gru_seq_fwd(Gi, W_hh, b_hh, want_saved=True):
+    """The whole time loop of one GRU layer in one launch (rec_gru_seq_fwd).  Gi [B,T,3H] = X W_ih^T + b_ih (gate order
+    r, z, c), W_hh [3H,H], b_hh [3H]; h_0 = 0.  -> (H_out [B,T,H], saved [B,T,5H] = r | z | c | hc | h_prev, or None)."""
+    B, T, H = _gru_dims(Gi, 3, "Gi")
+    _chk(W_hh, torch.float32, "W_hh", (3 * H, H))
+    _chk(b_hh, torch.float32, "b_hh", (3 * H,))
+    H_out = torch.empty(B, T, H, dtype=torch.float32, device=Gi.device)
+    saved = torch.empty(B, T, 5 * H, dtype=torch.float32, device=Gi.device) if want_saved else None
+    check(lib().rec_gru_seq_fwd(B, T, H, _p(Gi), _p(W_hh), _p(b_hh), _p(H_out), _p(saved), _stream()), "rec_gru_seq_fwd")
+    return H_out, saved
+
+
+def gru_seq_bwd(saved, W_hh, dH_out=None, dh_T=None):
+    """Backward through time in one launch (rec_gru_seq_bwd) from a per-step gradient dH_out [B,T,H] and / or a gradient
+    of the last state dh_T [B,H].  -> (dGi, dGh) [B,T,3H]."""
+    B, T, H = _gru_dims(saved, 5, "saved")
+    _chk(W_hh, torch.float32, "W_hh", (3 * H, H))
+    _chk(dH_out, torch.float32, "dH_out", (B, T, H))
+    _chk(dh_T, torch.float32, "dh_T", (B, H))
+    dGi = torch.empty(B, T, 3 * H, dtype=torch.float32, device=saved.device)
+    dGh = torch.empty(B, T, 3 * H, dtype=torch.float32, device=saved.device)
+    check(lib().rec_gru_seq_bwd(B, T, H, _p(saved), _p(W_hh), _p(dH_out), _p(dh_T), _p(dGi), _p(dGh), _stream()),
+          "rec_gru_seq_bwd")
+    return dGi, dGh
+
+
+def gru_layer_fwd(X, W_ih, W_hh, b_ih, b_hh, ws, want_saved=True):
+    """One GRU layer over X [B,T,E]: the input projection on rec_gemm_f32 (all B*T rows at once), the recurrence in
+    gru_seq_fwd.  W_ih [3H,E].  -> (H_out, saved)."""
+    _chk(X, torch.float32, "X")
+    if X.dim() != 3:
+        raise RecError("gru_layer_fwd: X must be [B, T, E]")
+    B, T, E = X.shape
+    H = W_hh.shape[1]
+    _chk(W_ih, torch.float32, "W_ih", (3 * H, E))
+    Gi = gemm(X.view(B * T, E), W_ih, ws, trans_b=True, epilogue="bias", bias=b_ih)
+    return gru_seq_fwd(Gi.view(B, T, 3 * H), W_hh, b_hh, want_saved=want_saved)
+
+
+def gru_layer_bwd(X, saved, W_ih, W_hh, ws, dW_ih, dW_hh, db_ih, db_hh, dH_out=None, dh_T=None, want_dX=True, dX_add=None):
+    """Backward of gru_layer_fwd: the time loop in gru_seq_bwd, then one GEMM each over the B*T rows — dW_ih = dGi^T X,
+    dW_hh = dGh^T H_prev, the bias gradients as column sums and dX = dGi W_ih (+ dX_add [B,T,E]).  -> dX | None."""
+    B, T, E = X.shape
+    dGi, dGh = gru_seq_bwd(saved, W_hh, dH_out=dH_out, dh_T=dh_T)
+    H = W_hh.shape[1]
+    gi, gh = dGi.view(B * T, 3 * H), dGh.view(B * T, 3 * H)
+    gemm(gi, X.view(B * T, E), ws, trans_a=True, out=dW_ih)
+    gemm(gh, saved.view(B * T, 5 * H)[:, 4 * H:], ws, trans_a=True, out=dW_hh)
+    colsum(gi, ws, out=db_ih)
+    colsum(gh, ws, out=db_hh)
+    if not want_dX:
+        return None
+    if dX_add is None:
+        return gemm(gi, W_ih, ws).view(B, T, E)
+    return gemm(gi, W_ih, ws, epilogue="add", aux1=dX_add.view(B * T, E)).view(B, T, E)
+
+
+def _dien_aux_args(gru_out, hist, neg_item, neg_cat, W_neg_item, W_neg_cat):
+    _chk(gru_out, torch.float32, "gru_out")
+    if gru_out.dim() != 3:
+        raise RecError("dien aux: gru_out must be [B, T, H]")
+    B, T, H = gru_out.shape
+    _chk(hist, torch.float32, "hist", (B, T, H))
+    _chk(neg_item, torch.int64, "neg_item", (B, T))
+    _chk(neg_cat, torch.int64, "neg_cat", (B, T))
+    Ei, si = _chk_table(W_neg_item, "W_neg_item")
+    Ec, sc = _chk_table(W_neg_cat, "W_neg_cat")
+    if Ei + Ec != H:
+        raise RecError("dien aux: item_dim %d + cat_dim %d != H %d" % (Ei, Ec, H))
+    return B, T, Ei, Ec, si, sc
+
+
+def dien_aux_fwd(gru_out, hist, neg_item, neg_cat, W_neg_item, W_neg_cat, ws, padding_idx=0, status=None, out=None):
+    """DIEN's auxiliary loss (rec_dien_aux_fwd; dien/net.py:219-254).  -> (aux [1], status)."""
+    B, T, Ei, Ec, si, sc = _dien_aux_args(gru_out, hist, neg_item, neg_cat, W_neg_item, W_neg_cat)
+    if out is None:
+        out = torch.empty(1, dtype=torch.float32, device=gru_out.device)
+    if status is None:
+        status = new_status(gru_out.device)
+    nbytes = C.c_size_t(0)
+    check(lib().rec_dien_aux_workspace_bytes(B, T, C.byref(nbytes)), "rec_dien_aux_workspace_bytes")
+    wk = ws.get(nbytes.value)
+    check(lib().rec_dien_aux_fwd(B, T, Ei, Ec, _p(gru_out), _p(hist), _p(neg_item), _p(neg_cat), _p(W_neg_item), si,
+                                 W_neg_item.shape[0], _p(W_neg_cat), sc, W_neg_cat.shape[0],
+                                 -1 if padding_idx is None else padding_idx, _p(out), _p(status), _p(wk),
+                                 C.c_size_t(wk.numel()), _stream()), "rec_dien_aux_fwd")
+    return out, status
+
+
+def dien_aux_bwd(gru_out, hist, neg_item, neg_cat, W_neg_item, W_neg_cat, d_hist, accumulate=True, d_aux=1.0,
+                 padding_idx=0, status=None):
+    """Backward of dien_aux_fwd (rec_dien_aux_bwd): d_hist [B,T,H] receives (accumulate: is added) the t+1-shifted
+    contribution.  -> (d_gru_out [B,T,H], d_neg [B,T,H])."""
+    B, T, Ei, Ec, si, sc = _dien_aux_args(gru_out, hist, neg_item, neg_cat, W_neg_item, W_neg_cat)
+    _chk(d_hist, torch.float32, "d_hist", (B, T, Ei + Ec))
+    d_go, d_neg = torch.empty_like(gru_out), torch.empty_like(gru_out)
+    if status is None:
+        status = new_status(gru_out.device)
+    check(lib().rec_dien_aux_bwd(B, T, Ei, Ec, _p(gru_out), _p(hist), _p(neg_item), _p(neg_cat), _p(W_neg_item), si,
+                                 W_neg_item.shape[0], _p(W_neg_cat), sc, W_neg_cat.shape[0],
+                                 -1 if padding_idx is None else padding_idx, float(d_aux), _p(d_go), _p(d_hist),
+                                 int(bool(accumulate)), _p(d_neg), _p(status), _stream()), "rec_dien_aux_bwd")
+    return d_go, d_neg
+
+
+def dien_att_feat_fwd(hist, q):
+    """feat [n, 4E] = [h, q, h - q, h * q] (rec_dien_att_feat_fwd); hist, q [.., E]."""
+    _chk(hist, torch.float32, "hist")
+    _chk(q, torch.float32, "q", tuple(hist.shape))
+    E = hist.shape[-1]
+    n = hist.numel() // E
+    feat = torch.empty(n, 4 * E, dtype=torch.float32, device=hist.device)
+    check(lib().rec_dien_att_feat_fwd(n, E, _p(hist), _p(q), _p(feat), _stream()), "rec_dien_att_feat_fwd")
+    return feat
+
+
+def dien_att_feat_bwd(hist, q, dfeat, d_hist, accumulate=True):
+    """d_hist (+)= d0 + d2 + d3 * q; -> d_q = d1 - d2 + d3 * h (rec_dien_att_feat_bwd)."""
+    E = hist.shape[-1]
+    n = hist.numel() // E
+    _chk(hist, torch.float32, "hist")
+    _chk(q, torch.float32, "q", tuple(hist.shape))
+    _chk(dfeat, torch.float32, "dfeat", (n, 4 * E))
+    _chk(d_hist, torch.float32, "d_hist", tuple(hist.shape))
+    d_q = torch.empty_like(hist)
+    check(lib().rec_dien_att_feat_bwd(n, E, _p(hist), _p(q), _p(dfeat), _p(d_hist), int(bool(accumulate)), _p(d_q),
+                                      _stream()), "rec_dien_att_feat_bwd")
+    return d_q
+
+
+def dien_softmax_weight_fwd(score, mask, hist, scale):
+    """w [B,T] = softmax_t((score + mask) * scale), x_att = w * hist (rec_dien_attention_seq_fwd)."""
+    _chk(hist, torch.float32, "hist")
+    if hist.dim() != 3:
+        raise RecError("dien attention seq: hist must be [B, T, E]")
+    B, T, E = hist.shape
+    _chk(score, torch.float32, "score")
+    _chk(mask, torch.float32, "mask")
+    if score.numel() != B * T or mask.numel() != B * T:
+        raise RecError("dien attention seq: score and mask must hold B * T floats")
+    w = torch.empty(B, T, dtype=torch.float32, device=hist.device)
+    x_att = torch.empty_like(hist)
+    check(lib().rec_dien_attention_seq_fwd(B, T, E, _p(score), _p(mask), _p(hist), float(scale), _p(w), _p(x_att),
+                                           _stream()), "rec_dien_attention_seq_fwd")
+    return w, x_att
+
+
+def dien_softmax_weight_bwd(w, hist, dx_att, scale, d_hist, accumulate=True):
+    """-> dscore [B,T] (the gradient of the attention MLP's output); d_hist (+)= w * dx_att (rec_dien_attention_seq_bwd)."""
+    B, T, E = hist.shape
+    _chk(w, torch.float32, "w", (B, T))
+    _chk(hist, torch.float32, "hist")
+    _chk(dx_att, torch.float32, "dx_att", (B, T, E))
+    _chk(d_hist, torch.float32, "d_hist", (B, T, E))
+    dscore = torch.empty(B, T, dtype=torch.float32, device=hist.device)
+    check(lib().rec_dien_attention_seq_bwd(B, T, E, _p(w), _p(hist), _p(dx_att), float(scale), _p(dscore), _p(d_hist),
+                                           int(bool(accumulate)), _stream()), "rec_dien_attention_seq_bwd")
+    return dscore
+
+
+def dien_attention_seq(hist, q, mask, att_w, att_b, ws):
+    """DIEN's position-wise attention (dien/net.py:192-209): features, the attention MLP on rec_gemm_f32 (sigmoids in the
+    epilogues), the scaled masked softmax over T and the weighting.  hist, q [B,T,E]; mask f32 [B,T] (0 / -1e9);
+    att_w [4E,H1],[H1,H2],[H2,1].  -> (w [B,T], x_att [B,T,E], saved = (feat, a1, a2) for the backward)."""
+    B, T, E = hist.shape
+    feat = dien_att_feat_fwd(hist, q)
+    a1 = gemm(feat, att_w[0], ws, epilogue="bias_sigmoid", bias=att_b[0])
+    a2 = gemm(a1, att_w[1], ws, epilogue="bias_sigmoid", bias=att_b[1])
+    score = gemm(a2, att_w[2], ws, epilogue="bias", bias=att_b[2])
+    w, x_att = dien_softmax_weight_fwd(score, mask, hist, float(E) ** -0.5)
+    return w, x_att, (feat, a1, a2)
+
+
+def dien_attention_seq_bwd(hist, q, w, saved, att_w, dx_att, d_hist, ws, accumulate=True):
+    """Backward of dien_attention_seq from dx_att [B,T,E]: d_hist (+)= the weighting's and the features' gradients;
+    -> d_q [B,T,E].  The attention MLP's weights get no gradient (they are not parameters of the reference's model)."""
+    B, T, E = hist.shape
+    _, a1, a2 = saved
+    dscore = dien_softmax_weight_bwd(w, hist, dx_att, float(E) ** -0.5, d_hist, accumulate=accumulate)
+    d2 = gemm(dscore.view(B * T, 1), att_w[2], ws, trans_b=True, epilogue="dsigmoid", aux0=a2)
+    d1 = gemm(d2, att_w[1], ws, trans_b=True, epilogue="dsigmoid", aux0=a1)
+    dfeat = gemm(d1, att_w[0], ws, trans_b=True)
+    return dien_att_feat_bwd(hist, q, dfeat, d_hist, accumulate=True)
+
+
 # ------------------------------------------------------------------ xDeepFM CIN (the passes around the GEMM)
 def _chk_f32(t, name):
     if not t.is_cuda:

@@ -428,3 +428,84 @@ class DinReader:
                         group = []
         if group:
             yield from self._emit(group, len(group) - len(group) % self.batch_size)
+
+
+class DienReader:
+    """models/rank/dien/dien_reader.py RecDataset: DIN's text format plus negative sampling.  Lines whose largest item id
+    exceeds item_count (or category id cat_count) are dropped; the kept samples are shuffled with random.seed(12345);
+    groups of 20*batch_size are sorted by history length (stable) and cut into batches padded to the batch's longest
+    history, and a batch whose longest history is below 2 is skipped.  Negatives come from two candidate pools (10000
+    items, 1000 categories) that persist over the reader's life and are drawn with Python's `random` in the reference's
+    call order — including its slip of writing a sample's CATEGORIES into the ITEM pool once the category pool is full
+    (dien_reader.py:137), and its slice assignment of len+1 slots, which shortens the pool by one.  Yields the ten feeds of
+    dien/dygraph_model.py:46-57 on `device`: hist_item, hist_cat [B,T] i64, target_item, target_cat [B] i64, label [B]
+    f32, mask [B,T,1] f32 (0 / -1e9), target_item_seq, target_cat_seq, neg_item, neg_cat [B,T] i64.  (The reference also
+    writes the longest history to ./tmp.txt — an unused side effect that is not reproduced.)"""
+    MAX_NEG_ITEM, MAX_NEG_CAT = 10000, 1000
+
+    def __init__(self, file_list, batch_size, device="cuda", item_count=63001, cat_count=801):
+        self.file_list, self.batch_size, self.device = list(file_list), int(batch_size), device
+        self.item_count, self.cat_count = item_count, cat_count
+        self.pool_item, self.pool_cat = [], []
+
+    def _negatives(self, sample, T):
+        import random
+        hist, cats = sample[0], sample[1]
+        if len(self.pool_item) < self.MAX_NEG_ITEM:
+            self.pool_item.extend(hist)
+            del self.pool_item[self.MAX_NEG_ITEM:]
+        else:
+            at = random.randint(0, self.MAX_NEG_ITEM - len(hist) - 1)
+            self.pool_item[at:at + len(hist) + 1] = hist
+        if len(self.pool_cat) < self.MAX_NEG_CAT:
+            self.pool_cat.extend(cats)
+            del self.pool_cat[self.MAX_NEG_CAT:]
+        else:
+            at = random.randint(0, self.MAX_NEG_CAT - len(cats) - 1)
+            self.pool_item[at:at + len(cats) + 1] = cats              # the reference's slip: the ITEM pool
+        ni = [self.pool_item[random.randint(0, len(self.pool_item) - 1)] for _ in range(T)]
+        nc = [self.pool_cat[random.randint(0, len(self.pool_cat) - 1)] for _ in range(T)]
+        return ni, nc
+
+    def _emit(self, group, upto):
+        B = self.batch_size
+        order = sorted(range(len(group)), key=lambda i: len(group[i][0]))       # stable, as sorted() in the reference
+        for i in range(0, upto, B):
+            b = [group[k] for k in order[i:i + B]]
+            T = max(len(x[0]) for x in b)
+            if T < 2:
+                continue
+            item, cat = np.zeros((len(b), T), np.int64), np.zeros((len(b), T), np.int64)
+            ni, nc = np.zeros((len(b), T), np.int64), np.zeros((len(b), T), np.int64)
+            lens = np.array([len(x[0]) for x in b])
+            for r, x in enumerate(b):
+                item[r, :len(x[0])], cat[r, :len(x[1])] = x[0], x[1]
+                ni[r], nc[r] = self._negatives(x, T)
+            ti, tc = np.array([x[2] for x in b], np.int64), np.array([x[3] for x in b], np.int64)
+            label = np.array([x[4] for x in b], np.float32)
+            mask = np.where(np.arange(T)[None, :] < lens[:, None], 0.0, -1e9).astype(np.float32).reshape(-1, T, 1)
+            arrs = (item, cat, ti, tc, label, mask, np.repeat(ti[:, None], T, 1), np.repeat(tc[:, None], T, 1), ni, nc)
+            yield tuple(torch.from_numpy(np.ascontiguousarray(a)).to(self.device, non_blocking=True) for a in arrs)
+
+    def __iter__(self):
+        import random
+        data = []
+        for path in self.file_list:
+            with open(path, "r") as f:
+                for line in f:
+                    parts = line.strip().split(";")
+                    if len(parts) != 5:
+                        continue
+                    hist, cats = [int(x) for x in parts[0].split()], [int(x) for x in parts[1].split()]
+                    if max(hist) > self.item_count or max(cats) > self.cat_count:
+                        continue
+                    data.append((hist, cats, int(parts[2]), int(parts[3]), float(parts[4])))
+        random.seed(12345)
+        random.shuffle(data)
+        gsz = self.batch_size * 20
+        full = len(data) - len(data) % gsz
+        for s in range(0, full, gsz):
+            yield from self._emit(data[s:s + gsz], gsz)
+        tail = data[full:]
+        if tail:
+            yield from self._emit(tail, len(tail) - len(tail) % self.batch_size)
