@@ -1697,6 +1697,85 @@ int rec_dien_attention_seq_bwd(int64_t batch, int32_t steps, int32_t emb_dim, co
                                const float* dx_att, float scale, float* dscore, float* d_hist, int32_t accumulate_hist,
                                void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * DMR (models/rank/dmr/net.py, Deep Match to Rank) — csrc/dmr_ops.hip.  Every sum has a fixed order: reruns are
+ * bit-identical.  P = float32(-2^32 + 1) = -4294967296 is the reference's padding score.
+ *
+ * rec_dmr_prefix_pool_fwd (net.py:259-281 for a LIST of rows of the [B,T,T] tile; net.py:338-350 with the one row T-1):
+ *   score [batch, steps]; mask [batch, steps] i64 (row stride ld_mask), valid iff == 1; hist[b,j,:] at hist + (b * steps
+ *   + j) * ld_hist; rows[num_rows] (HOST memory, 1 <= num_rows <= 8, each in [0, steps)).  For every listed row r:
+ *     v_j = (j <= r && mask_j == 1) ? score_j : P   for ALL j < steps;   w_r = softmax(v) (f32, maximum subtracted)
+ *     out[b, r, :] = sum_j w_{r,j} hist[b,j,:]  (ascending j)   at out + b * ld_out + r * dim
+ *   A prefix without a valid position has max = P and comes out uniform 1 / steps over ALL positions, as in the
+ *   reference.  rel (nullable): rel[b * ld_rel] = sum_j (mask_j == 1 ? score_j : 0).  w [batch, num_rows, steps] is saved.
+ * rec_dmr_prefix_pool_bwd: g_{r,j} = d_out[b,r] . hist[b,j];  dv_{r,j} = w_{r,j} (g_{r,j} - sum_s w_{r,s} g_{r,s});
+ *   dscore[b,j] = sum_r [j <= r && mask_j == 1] dv_{r,j} + [mask_j == 1] d_rel[b * ld_drel]   (d_rel nullable; a padded
+ *   entry gets no gradient even where its weight is 1 / steps);  d_hist[b,j,:] (+)= sum_r w_{r,j} d_out[b,r,:]
+ *   (accumulate_hist 0: written).  steps <= 4096.
+ * ---------------------------------------------------------------------------------------- */
+int rec_dmr_prefix_pool_fwd(int64_t batch, int32_t steps, int32_t dim, const float* score, const int64_t* mask,
+                            int64_t ld_mask, const float* hist, int64_t ld_hist, int32_t num_rows, const int32_t* rows,
+                            float* out, int64_t ld_out, float* rel, int64_t ld_rel, float* w, void* stream);
+int rec_dmr_prefix_pool_bwd(int64_t batch, int32_t steps, int32_t dim, const int64_t* mask, int64_t ld_mask,
+                            const float* hist, int64_t ld_hist, int32_t num_rows, const int32_t* rows, const float* w,
+                            const float* d_out, int64_t ld_dout, const float* d_rel, int64_t ld_drel, float* dscore,
+                            float* d_hist, int64_t ld_dhist, int32_t accumulate_hist, void* stream);
+
+/* paddle.nn.PReLU on X [m, n] (row strides): y = x > 0 ? x : alpha[ch] * x.  row_mode 0: ch = column (num_alpha == n;
+ * n = 1 is one shared slope).  row_mode 1: ch = base + row % period (axis 1 of a [B, period, n] input given as
+ * [B * period, n]; base + period <= num_alpha).
+ * rec_prelu_bwd: dX = x > 0 ? dy : alpha[ch] dy;  dalpha[ch] = sum of dy * x over x <= 0 — ALL num_alpha entries are
+ * written (0 for a channel the call does not reach); per-block partials in the workspace, folded in a fixed order. */
+int rec_prelu_fwd(int64_t m, int32_t n, const float* X, int64_t ldx, const float* alpha, int32_t num_alpha,
+                  int32_t row_mode, int32_t period, int32_t base, float* Y, int64_t ldy, void* stream);
+int rec_prelu_workspace_bytes(int64_t m, int32_t n, int32_t row_mode, int32_t period, size_t* bytes);
+int rec_prelu_bwd(int64_t m, int32_t n, const float* X, int64_t ldx, const float* dY, int64_t lddy, const float* alpha,
+                  int32_t num_alpha, int32_t row_mode, int32_t period, int32_t base, float* dX, int64_t lddx,
+                  float* dalpha, void* workspace, size_t workspace_bytes, void* stream);
+
+/* DMR's auxiliary match loss (net.py:298-301): logits = U V^T + bias over ALL classes, mean softmax cross-entropy.
+ * U [batch, k], V [classes, k] (row strides multiples of 4, 16-byte aligned; k a multiple of 4, <= 64), bias [classes]
+ * nullable, label[b * ld_label] i64.  No buffer of batch x classes elements exists: the classes are cut into at most 64
+ * chunks whose (max, sum exp) are folded in chunk order; plain f32 FMAs.
+ *   lse[b] = log sum_c exp(logit[b,c]);   loss[0] = (1 / batch) sum_b (lse[b] - logit[b, label_b])
+ * A label outside [0, classes) raises REC_FLAG_INDEX_OOB; such a row contributes its lse alone.
+ * rec_dmr_match_loss_bwd recomputes the logits: G[b,c] = (d_loss / batch) (exp(logit - lse_b) - [c == label_b]);
+ *   dU[b,:] = sum_c G[b,c] V[c,:];   dV[c,:] (+)= sum_b G[b,c] U[b,:] for EVERY class (accumulate_dv 0: written).
+ * Workspaces: rec_dmr_match_loss_workspace_bytes (forward: (max, sum) per row and chunk; backward: the larger of the
+ * per-chunk dU partials [batch, 64, k] and the per-batch-chunk dV partials [16, classes, k]); 16-byte aligned. */
+int rec_dmr_match_loss_workspace_bytes(int64_t batch, int64_t classes, int32_t k, size_t* fwd_bytes, size_t* bwd_bytes);
+int rec_dmr_match_loss_fwd(int64_t batch, int64_t classes, int32_t k, const float* U, int64_t ldu, const float* V,
+                           int64_t ldv, const float* bias, const int64_t* label, int64_t ld_label, float* loss,
+                           float* lse, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+int rec_dmr_match_loss_bwd(int64_t batch, int64_t classes, int32_t k, const float* U, int64_t ldu, const float* V,
+                           int64_t ldv, const float* bias, const int64_t* label, int64_t ld_label, const float* lse,
+                           float d_loss, float* dU, int64_t lddu, float* dV, int64_t lddv, int32_t accumulate_dv,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
+/* The glue of DMR's tower input (net.py:471, 289-291, 512-516, 526), written straight into column ranges of `inp`:
+ * rec_dmr_tail_fwd: hist_sum[b,:] = sum_t hist[b,t,:] over ALL t (the reference ignores the mask); prod = item_eb *
+ *   hist_sum; rel_u2i[b] = uv[b,1,:] . V[cate_id[b]];  U2[b,:] = uv[b,0,:] * float(match_mask[b * ld_mm]).  dim = the
+ *   width of hist / item_eb; uv [batch, 2, dim / 2] = the PReLU'd rows T-2 and T-1; U2 [batch, dim / 2].  A cate_id
+ *   outside [0, classes) reads as a zero row and raises REC_FLAG_INDEX_OOB.
+ * rec_dmr_tail_bwd_match: d_uv[b,0,:] = dU2[b,:] * match_mask[b] (dU2 nullable: 0);  d_uv[b,1,:] = d_rel[b] V[cate_id[b]];
+ *   dV_rows[b,:] = d_rel[b] uv[b,1,:] (the gradient of the cate_id lookup of V).
+ * rec_dmr_tail_bwd_hist: d_hist[b,t,:] += f1[b,t,:] + f2[b,t,:] + d_sum[b,:] + d_prod[b,:] * item_eb[b,:]  (f1, f2
+ *   [batch, steps, dim] contiguous, nullable);  d_item[b,:] = d_item_direct[b,:] + d_prod[b,:] * hist_sum[b,:] +
+ *   sum_t d_ctx[(b * steps + t) * ld_ctx + :]  (ascending t: the tiled item_eb of net.py:311-319). */
+int rec_dmr_tail_fwd(int64_t batch, int32_t steps, int32_t dim, const float* hist, int64_t ld_hist, const float* item_eb,
+                     int64_t ld_item, const float* uv, const int64_t* match_mask, int64_t ld_mm, const float* V,
+                     int64_t ldv, int64_t classes, const int64_t* cate_id, float* hist_sum, int64_t ld_sum, float* prod,
+                     int64_t ld_prod, float* rel_u2i, int64_t ld_rel, float* U2, int32_t* status, void* stream);
+int rec_dmr_tail_bwd_match(int64_t batch, int32_t half_dim, const float* dU2, const float* d_rel, int64_t ld_drel,
+                           const float* uv, const int64_t* match_mask, int64_t ld_mm, const float* V, int64_t ldv,
+                           int64_t classes, const int64_t* cate_id, float* d_uv, float* dV_rows, int64_t ld_dvr,
+                           void* stream);
+int rec_dmr_tail_bwd_hist(int64_t batch, int32_t steps, int32_t dim, const float* f1, const float* f2, const float* d_sum,
+                          int64_t ld_dsum, const float* d_prod, int64_t ld_dprod, const float* item_eb, int64_t ld_item,
+                          const float* hist_sum, int64_t ld_sum, const float* d_item_direct, int64_t ld_did,
+                          const float* d_ctx, int64_t ld_ctx, float* d_hist, int64_t ld_dhist, float* d_item,
+                          int64_t ld_ditem, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -265,6 +265,21 @@ SIGNATURES = {
     "rec_dien_att_feat_bwd": (C.c_int, [_I64, _I32, _P, _P, _P, _P, _I32, _P, _P]),
     "rec_dien_attention_seq_fwd": (C.c_int, [_I64, _I32, _I32, _P, _P, _P, _F, _P, _P, _P]),
     "rec_dien_attention_seq_bwd": (C.c_int, [_I64, _I32, _I32, _P, _P, _P, _F, _P, _P, _I32, _P]),
+    "rec_dmr_prefix_pool_fwd": (C.c_int, [_I64, _I32, _I32, _P, _P, _I64, _P, _I64, _I32, _P, _P, _I64, _P, _I64, _P, _P]),
+    "rec_dmr_prefix_pool_bwd": (C.c_int, [_I64, _I32, _I32, _P, _I64, _P, _I64, _I32, _P, _P, _P, _I64, _P, _I64, _P, _P,
+                                          _I64, _I32, _P]),
+    "rec_prelu_fwd": (C.c_int, [_I64, _I32, _P, _I64, _P, _I32, _I32, _I32, _I32, _P, _I64, _P]),
+    "rec_prelu_workspace_bytes": (C.c_int, [_I64, _I32, _I32, _I32, C.POINTER(_SZ)]),
+    "rec_prelu_bwd": (C.c_int, [_I64, _I32, _P, _I64, _P, _I64, _P, _I32, _I32, _I32, _I32, _P, _I64, _P, _P, _SZ, _P]),
+    "rec_dmr_match_loss_workspace_bytes": (C.c_int, [_I64, _I64, _I32, C.POINTER(_SZ), C.POINTER(_SZ)]),
+    "rec_dmr_match_loss_fwd": (C.c_int, [_I64, _I64, _I32, _P, _I64, _P, _I64, _P, _P, _I64, _P, _P, _P, _P, _SZ, _P]),
+    "rec_dmr_match_loss_bwd": (C.c_int, [_I64, _I64, _I32, _P, _I64, _P, _I64, _P, _P, _I64, _P, _F, _P, _I64, _P, _I64,
+                                         _I32, _P, _SZ, _P]),
+    "rec_dmr_tail_fwd": (C.c_int, [_I64, _I32, _I32, _P, _I64, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _P, _P, _I64, _P,
+                                   _I64, _P, _I64, _P, _P, _P]),
+    "rec_dmr_tail_bwd_match": (C.c_int, [_I64, _I32, _P, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _P, _P, _P, _I64, _P]),
+    "rec_dmr_tail_bwd_hist": (C.c_int, [_I64, _I32, _I32, _P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P,
+                                        _I64, _P, _I64, _P, _I64, _P]),
     "rec_dense_fold_fwd": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P]),
     "rec_dense_fold_bwd": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _I32, _P]),
     "rec_dense_fold_fwd_full": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P]),

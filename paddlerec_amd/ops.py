@@ -2038,6 +2038,225 @@ def dien_attention_seq_bwd(hist, q, w, saved, att_w, dx_att, d_hist, ws, accumul
     return dien_att_feat_bwd(hist, q, dfeat, d_hist, accumulate=True)
 
 
+# ------------------------------------------------------------------ DMR (rank/dmr): prefix pool, PReLU, match loss, tail glue
+def _view_ld(t):
+    """Row stride (floats / ids) of a 2-D view with unit column stride."""
+    if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise RecError("expected a 2-D view with unit column stride, got shape %s strides %s" % (tuple(t.shape), t.stride()))
+    return t.stride(0) if t.shape[0] > 1 else max(t.shape[1], 1)
+
+
+def _dev(t, dtype, name):
+    if t is None:
+        return
+    if not t.is_cuda:
+        raise RecError("%s must be a device tensor (no CPU fallback)" % name)
+    if t.dtype != dtype:
+        raise RecError("%s must be %s, got %s" % (name, dtype, t.dtype))
+
+
+def _pool_args(score, mask, hist, rows):
+    _chk(score, torch.float32, "score")
+    _dev(mask, torch.int64, "mask")
+    _dev(hist, torch.float32, "hist")
+    if hist.dim() != 3 or hist.stride(2) != 1 or (hist.shape[0] > 1 and hist.stride(0) != hist.shape[1] * hist.stride(1)):
+        raise RecError("dmr prefix pool: hist must be [B, T, D] with one row stride")
+    B, T, D = hist.shape
+    if score.numel() != B * T or tuple(mask.shape) != (B, T):
+        raise RecError("dmr prefix pool: score and mask must be [B, T]")
+    rows = [int(r) for r in rows]
+    if not 1 <= len(rows) <= 8 or any(not 0 <= r < T for r in rows):
+        raise RecError("dmr prefix pool: rows must be 1..8 positions in [0, T), got %s" % (rows,))
+    return B, T, D, rows, (C.c_int32 * len(rows))(*rows)
+
+
+def dmr_prefix_pool_fwd(score, mask, hist, rows, out=None, rel=None):
+    """Causal masked-softmax pooling for the listed query positions (rec_dmr_prefix_pool_fwd; dmr/net.py:259-281 and
+    338-350).  score [B,T] f32, mask [B,T] i64 (valid iff 1; a strided view is fine), hist [B,T,D] (row stride allowed).
+    out: a [B, R*D] view (row stride allowed) or None; rel: a [B,1] view (the sum of the raw scores at valid positions) or
+    None.  -> (out [B,R*D], w [B,R,T])."""
+    B, T, D, rows, crows = _pool_args(score, mask, hist, rows)
+    R = len(rows)
+    if out is None:
+        out = torch.empty(B, R * D, dtype=torch.float32, device=hist.device)
+    _dev(out, torch.float32, "out")
+    _dev(rel, torch.float32, "rel")
+    if tuple(out.shape) != (B, R * D) or (rel is not None and tuple(rel.shape) != (B, 1)):
+        raise RecError("dmr prefix pool: out must be [B, R*D] and rel [B, 1]")
+    w = torch.empty(B, R, T, dtype=torch.float32, device=hist.device)
+    check(lib().rec_dmr_prefix_pool_fwd(B, T, D, _p(score), _p(mask), _view_ld(mask), _p(hist), hist.stride(1), R, crows,
+                                        _p(out), _view_ld(out), _p(rel), _view_ld(rel) if rel is not None else 0, _p(w), _stream()),
+          "rec_dmr_prefix_pool_fwd")
+    return out, w
+
+
+def dmr_prefix_pool_bwd(mask, hist, rows, w, d_out, d_hist, d_rel=None, accumulate=True):
+    """Backward of dmr_prefix_pool_fwd: d_out [B, R*D] view, d_rel [B,1] view or None; d_hist [B,T,D] (row stride allowed)
+    receives (accumulate: is added) sum_r w d_out.  -> dscore [B,T]."""
+    B, T, D = hist.shape
+    rows = [int(r) for r in rows]
+    R = len(rows)
+    _chk(w, torch.float32, "w", (B, R, T))
+    for t, n in ((hist, "hist"), (d_out, "d_out"), (d_hist, "d_hist"), (d_rel, "d_rel")):
+        _dev(t, torch.float32, n)
+    _dev(mask, torch.int64, "mask")
+    if tuple(d_out.shape) != (B, R * D) or tuple(d_hist.shape) != (B, T, D) or d_hist.stride(2) != 1 or \
+            (B > 1 and d_hist.stride(0) != T * d_hist.stride(1)) or (d_rel is not None and tuple(d_rel.shape) != (B, 1)):
+        raise RecError("dmr prefix pool bwd: d_out must be [B, R*D], d_hist [B, T, D] with one row stride, d_rel [B, 1]")
+    if not 1 <= R <= 8 or any(not 0 <= r < T for r in rows):
+        raise RecError("dmr prefix pool: rows must be 1..8 positions in [0, T), got %s" % (rows,))
+    dscore = torch.empty(B, T, dtype=torch.float32, device=hist.device)
+    check(lib().rec_dmr_prefix_pool_bwd(B, T, D, _p(mask), _view_ld(mask), _p(hist), hist.stride(1), R,
+                                        (C.c_int32 * R)(*rows), _p(w), _p(d_out), _view_ld(d_out), _p(d_rel),
+                                        _view_ld(d_rel) if d_rel is not None else 0, _p(dscore), _p(d_hist), d_hist.stride(1),
+                                        int(bool(accumulate)), _stream()), "rec_dmr_prefix_pool_bwd")
+    return dscore
+
+
+def prelu_fwd(X, alpha, period=0, base=0, out=None):
+    """paddle.nn.PReLU on X [m, n] (rec_prelu_fwd).  period 0: the channel is the column (alpha [n]); period > 0: the
+    channel is base + row % period (axis 1 of a [B, period, n] input given as [B*period, n])."""
+    ldx = _chk_mat(X, "X")
+    _chk(alpha, torch.float32, "alpha")
+    m, n = X.shape
+    if out is None:
+        out = torch.empty(m, n, dtype=torch.float32, device=X.device)
+    check(lib().rec_prelu_fwd(m, n, _p(X), ldx, _p(alpha), alpha.numel(), int(period > 0), int(period), int(base), _p(out),
+                              _chk_mat(out, "out"), _stream()), "rec_prelu_fwd")
+    return out
+
+
+def prelu_bwd(X, dY, alpha, ws, period=0, base=0, dalpha=None, out=None):
+    """-> (dX, dalpha [alpha.numel()]): dX = x > 0 ? dy : alpha dy; dalpha[ch] = sum of dy x over x <= 0, every entry
+    written (rec_prelu_bwd)."""
+    ldx, lddy = _chk_mat(X, "X"), _chk_mat(dY, "dY")
+    _chk(alpha, torch.float32, "alpha")
+    m, n = X.shape
+    if tuple(dY.shape) != (m, n):
+        raise RecError("prelu_bwd: dY has shape %s, expected %s" % (tuple(dY.shape), (m, n)))
+    if out is None:
+        out = torch.empty(m, n, dtype=torch.float32, device=X.device)
+    if dalpha is None:
+        dalpha = torch.empty(alpha.numel(), dtype=torch.float32, device=X.device)
+    _chk(dalpha, torch.float32, "dalpha")
+    if dalpha.numel() != alpha.numel():
+        raise RecError("prelu_bwd: dalpha must have alpha's size")
+    nbytes = C.c_size_t(0)
+    check(lib().rec_prelu_workspace_bytes(m, n, int(period > 0), int(period), C.byref(nbytes)), "rec_prelu_workspace_bytes")
+    wk = ws.get(nbytes.value)
+    check(lib().rec_prelu_bwd(m, n, _p(X), ldx, _p(dY), lddy, _p(alpha), alpha.numel(), int(period > 0), int(period),
+                              int(base), _p(out), _chk_mat(out, "dX"), _p(dalpha), _p(wk), C.c_size_t(wk.numel()),
+                              _stream()), "rec_prelu_bwd")
+    return out, dalpha
+
+
+def _match_args(U, V, bias, label):
+    ldu, ldv = _chk_mat(U, "U"), _chk_mat(V, "V")
+    B, K = U.shape
+    Cn = V.shape[0]
+    if V.shape[1] != K:
+        raise RecError("dmr match loss: U is [B, %d] but V [C, %d]" % (K, V.shape[1]))
+    _chk(bias, torch.float32, "bias", (Cn,))
+    _dev(label, torch.int64, "label")
+    if label.dim() != 1 or label.shape[0] != B:
+        raise RecError("dmr match loss: label must be [B] (a strided view is fine)")
+    fb, bb = C.c_size_t(0), C.c_size_t(0)
+    check(lib().rec_dmr_match_loss_workspace_bytes(B, Cn, K, C.byref(fb), C.byref(bb)), "rec_dmr_match_loss_workspace_bytes")
+    return B, Cn, K, ldu, ldv, (label.stride(0) if B > 1 else 1), fb.value, bb.value
+
+
+def dmr_match_loss_fwd(U, V, bias, label, ws, status=None):
+    """Mean softmax cross-entropy of U V^T + bias over ALL classes without a [B, C] buffer (rec_dmr_match_loss_fwd;
+    dmr/net.py:298-301).  U [B,K], V [C,K], bias [C] or None, label [B] i64.  -> (loss [1], lse [B], status)."""
+    B, Cn, K, ldu, ldv, ldl, fb, _ = _match_args(U, V, bias, label)
+    loss = torch.empty(1, dtype=torch.float32, device=U.device)
+    lse = torch.empty(B, dtype=torch.float32, device=U.device)
+    if status is None:
+        status = new_status(U.device)
+    wk = ws.get(fb)
+    check(lib().rec_dmr_match_loss_fwd(B, Cn, K, _p(U), ldu, _p(V), ldv, _p(bias), _p(label), ldl, _p(loss), _p(lse),
+                                       _p(status), _p(wk), C.c_size_t(wk.numel()), _stream()), "rec_dmr_match_loss_fwd")
+    return loss, lse, status
+
+
+def dmr_match_loss_bwd(U, V, bias, label, lse, d_loss, dV, ws, accumulate=False):
+    """Backward of dmr_match_loss_fwd (the logits are recomputed): dV [C,K] (row stride allowed) receives (accumulate: is
+    added) the DENSE gradient of every class row.  -> dU [B,K]."""
+    B, Cn, K, ldu, ldv, ldl, _, bb = _match_args(U, V, bias, label)
+    _chk(lse, torch.float32, "lse", (B,))
+    lddv = _chk_mat(dV, "dV")
+    if tuple(dV.shape) != (Cn, K):
+        raise RecError("dmr match loss: dV must be [C, K]")
+    dU = torch.empty(B, K, dtype=torch.float32, device=U.device)
+    wk = ws.get(bb)
+    check(lib().rec_dmr_match_loss_bwd(B, Cn, K, _p(U), ldu, _p(V), ldv, _p(bias), _p(label), ldl, _p(lse), float(d_loss),
+                                       _p(dU), K, _p(dV), lddv, int(bool(accumulate)), _p(wk), C.c_size_t(wk.numel()),
+                                       _stream()), "rec_dmr_match_loss_bwd")
+    return dU
+
+
+def dmr_tail_fwd(hist, item_eb, uv, match_mask, V, cate_id, hist_sum, prod, rel_u2i, status):
+    """The glue of DMR's tower input (rec_dmr_tail_fwd): hist_sum = sum_t hist (unmasked), prod = item_eb * hist_sum,
+    rel_u2i = uv[:,1] . V[cate_id], all written into the given [B, .] views; -> U2 [B,E] = uv[:,0] * match_mask.
+    hist [B,T,2E]; item_eb, hist_sum, prod [B,2E] views; uv [B,2,E]; match_mask [B,1] i64 view; rel_u2i [B,1] view."""
+    B, T, D = hist.shape
+    _chk(uv, torch.float32, "uv", (B, 2, D // 2))
+    _chk(cate_id, torch.int64, "cate_id", (B,))
+    for t, n in ((hist, "hist"), (item_eb, "item_eb"), (hist_sum, "hist_sum"), (prod, "prod"), (rel_u2i, "rel_u2i")):
+        _dev(t, torch.float32, n)
+    _dev(match_mask, torch.int64, "match_mask")
+    ldv = _chk_mat(V, "V")
+    if D % 2 or V.shape[1] != D // 2 or any(tuple(t.shape) != (B, D) for t in (item_eb, hist_sum, prod)) or \
+            tuple(rel_u2i.shape) != (B, 1) or tuple(match_mask.shape) != (B, 1):
+        raise RecError("dmr_tail_fwd: shapes do not fit hist [B, T, 2E]")
+    U2 = torch.empty(B, D // 2, dtype=torch.float32, device=hist.device)
+    check(lib().rec_dmr_tail_fwd(B, T, D, _p(hist), hist.stride(1), _p(item_eb), _view_ld(item_eb), _p(uv), _p(match_mask),
+                                 _view_ld(match_mask), _p(V), ldv, V.shape[0], _p(cate_id), _p(hist_sum), _view_ld(hist_sum), _p(prod),
+                                 _view_ld(prod), _p(rel_u2i), _view_ld(rel_u2i), _p(U2), _p(status), _stream()), "rec_dmr_tail_fwd")
+    return U2
+
+
+def dmr_tail_bwd_match(dU2, d_rel, uv, match_mask, V, cate_id, dV_rows):
+    """-> d_uv [B,2,E]: row 0 = dU2 * match_mask (dU2 None: 0), row 1 = d_rel V[cate_id]; dV_rows [B,E] view = d_rel
+    uv[:,1] (rec_dmr_tail_bwd_match)."""
+    B, _, E = uv.shape
+    _chk(uv, torch.float32, "uv")
+    _chk(dU2, torch.float32, "dU2", (B, E))
+    _chk(cate_id, torch.int64, "cate_id", (B,))
+    _dev(d_rel, torch.float32, "d_rel")
+    _dev(dV_rows, torch.float32, "dV_rows")
+    _dev(match_mask, torch.int64, "match_mask")
+    if tuple(d_rel.shape) != (B, 1) or tuple(dV_rows.shape) != (B, E) or tuple(match_mask.shape) != (B, 1):
+        raise RecError("dmr_tail_bwd_match: d_rel / match_mask must be [B, 1] and dV_rows [B, E]")
+    d_uv = torch.empty(B, 2, E, dtype=torch.float32, device=uv.device)
+    check(lib().rec_dmr_tail_bwd_match(B, E, _p(dU2), _p(d_rel), _view_ld(d_rel), _p(uv), _p(match_mask), _view_ld(match_mask), _p(V),
+                                       _chk_mat(V, "V"), V.shape[0], _p(cate_id), _p(d_uv), _p(dV_rows), _view_ld(dV_rows),
+                                       _stream()), "rec_dmr_tail_bwd_match")
+    return d_uv
+
+
+def dmr_tail_bwd_hist(f1, f2, d_sum, d_prod, item_eb, hist_sum, d_item_direct, d_ctx, d_hist, d_item):
+    """d_hist [B,T,D] += f1 + f2 + d_sum + d_prod * item_eb (broadcast over T); d_item [B,D] = d_item_direct + d_prod *
+    hist_sum + sum_t d_ctx[b,t,:D] (rec_dmr_tail_bwd_hist).  f1, f2 [B,T,D] contiguous or None; d_ctx [B*T, >= D] view."""
+    B, T, D = d_hist.shape
+    _chk(f1, torch.float32, "f1", (B, T, D))
+    _chk(f2, torch.float32, "f2", (B, T, D))
+    for t, n in ((d_sum, "d_sum"), (d_prod, "d_prod"), (item_eb, "item_eb"), (hist_sum, "hist_sum"),
+                 (d_item_direct, "d_item_direct"), (d_item, "d_item")):
+        _dev(t, torch.float32, n)
+        if tuple(t.shape) != (B, D):
+            raise RecError("dmr_tail_bwd_hist: %s must be [B, D]" % n)
+    _dev(d_ctx, torch.float32, "d_ctx")
+    _dev(d_hist, torch.float32, "d_hist")
+    if d_ctx.shape[0] != B * T or d_ctx.shape[1] < D or d_hist.stride(2) != 1 or \
+            (B > 1 and d_hist.stride(0) != T * d_hist.stride(1)):
+        raise RecError("dmr_tail_bwd_hist: d_ctx must be [B*T, >= D] and d_hist [B, T, D] with one row stride")
+    check(lib().rec_dmr_tail_bwd_hist(B, T, D, _p(f1), _p(f2), _p(d_sum), _view_ld(d_sum), _p(d_prod), _view_ld(d_prod), _p(item_eb),
+                                      _view_ld(item_eb), _p(hist_sum), _view_ld(hist_sum), _p(d_item_direct), _view_ld(d_item_direct),
+                                      _p(d_ctx), _view_ld(d_ctx), _p(d_hist), d_hist.stride(1), _p(d_item), _view_ld(d_item),
+                                      _stream()), "rec_dmr_tail_bwd_hist")
+
+
 # ------------------------------------------------------------------ xDeepFM CIN (the passes around the GEMM)
 def _chk_f32(t, name):
     if not t.is_cuda:

@@ -509,3 +509,38 @@ class DienReader:
         tail = data[full:]
         if tail:
             yield from self._emit(tail, len(tail) - len(tail) % self.batch_size)
+
+
+class AlimamaReader:
+    """models/rank/dmr/alimama_reader.py RecDataset with the batching of the other readers (drop_last over the
+    concatenation of the files): comma-separated lines of 267 fields; '' and NULL (any case) read as 0; every value goes
+    through float32 and is then truncated to int64, as np.array(l).astype('float32') followed by
+    dygraph_model.py:63's astype('int64') does.  Yields (sparse [B, 267] i64, price [B, 1] f32 = column 264) on
+    `device`; the label is the last column of sparse.  A line with another field count is an error (the reference's
+    batching would fail on it)."""
+    FIELDS, PRICE_COL = 267, 264
+
+    def __init__(self, file_list, batch_size, device="cuda"):
+        self.file_list, self.batch_size, self.device = list(file_list), int(batch_size), device
+
+    def _rows(self):
+        for path in self.file_list:
+            with open(path, "r") as f:
+                for no, line in enumerate(f, 1):
+                    parts = line.strip().split(",")
+                    if parts == [""]:
+                        continue
+                    if len(parts) != self.FIELDS:
+                        raise ValueError("%s:%d has %d fields, expected %d" % (path, no, len(parts), self.FIELDS))
+                    yield ["0" if x == "" or x.upper() == "NULL" else x for x in parts]
+
+    def __iter__(self):
+        group = []
+        for row in self._rows():
+            group.append(row)
+            if len(group) == self.batch_size:
+                arr = np.asarray(group).astype(np.float32)
+                group = []
+                sparse = torch.from_numpy(arr.astype(np.int64))
+                price = torch.from_numpy(np.ascontiguousarray(arr[:, self.PRICE_COL:self.PRICE_COL + 1]))
+                yield sparse.to(self.device, non_blocking=True), price.to(self.device, non_blocking=True)
