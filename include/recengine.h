@@ -1776,6 +1776,71 @@ int rec_dmr_tail_bwd_hist(int64_t batch, int32_t steps, int32_t dim, const float
                           const float* d_ctx, int64_t ld_ctx, float* d_hist, int64_t ld_dhist, float* d_item,
                           int64_t ld_ditem, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * BST (models/rank/bst/net.py): the Transformer encoder block.  All float32, fixed summation order, no float atomics.
+ *
+ * rec_mha_fwd: multi-head attention over [batch, seq_len] tokens (net.py:339-394 between the q / k / v Linears and
+ *   po_liner).  q, k: [batch * seq_len, >= n_head * d_k], v: [.., >= n_head * d_v] with row strides ldq / ldk / ldv — three
+ *   column ranges of one packed projection output, or separate matrices; head h is columns h * d .. (h + 1) * d.
+ *     out[b*L + i, h*d_v : (h+1)*d_v] = sum_j drop(softmax_j(scale * q_i . k_j)) v_j     (the combined-heads layout)
+ *     lse[(b*n_head + h)*L + i]       = log sum_j exp(scale * q_i . k_j)
+ *   No [batch, n_head, L, L] array is written, forward or backward: keys and values are walked in tiles with the running
+ *   maximum subtracted.  Limits: 1 <= seq_len <= 8192; d_k, d_v multiples of 4 in [4, 64]; every pointer 16-byte aligned
+ *   and every row stride a multiple of 4.  scale is the factor on the scores (bst passes 1: net.py:366 does not scale).
+ *   Dropout on the weights (upscale_in_train): element e = ((b*n_head + h)*L + i)*L + j is kept by rec_dropout's rule for
+ *   (p, seed, stream_id) — rec_dropout on ones of shape [batch*n_head*L, L] reproduces the mask.  p = 0 skips the hashing.
+ * rec_mha_bwd: recomputes the weights from lse; delta [batch*n_head*L] scratch (receives D_i = sum_j P_ij dP_ij / sum_j
+ *   P_ij, summed over the recomputed weights in a sweep of its own; `out`, the forward's output, is validated and not
+ *   read — dO_i . O_i is the same number only in exact arithmetic).  dq, dk, dv with their own row strides (column ranges of one packed gradient are fine); they
+ *   alias no input and not each other.
+ * ---------------------------------------------------------------------------------------- */
+int rec_mha_fwd(int64_t batch, int32_t seq_len, int32_t n_head, int32_t d_k, int32_t d_v, const float* q, int64_t ldq,
+                const float* k, int64_t ldk, const float* v, int64_t ldv, float scale, float p, uint64_t seed,
+                uint64_t stream_id, float* out, int64_t ldo, float* lse, void* stream);
+int rec_mha_bwd(int64_t batch, int32_t seq_len, int32_t n_head, int32_t d_k, int32_t d_v, const float* q, int64_t ldq,
+                const float* k, int64_t ldk, const float* v, int64_t ldv, float scale, float p, uint64_t seed,
+                uint64_t stream_id, const float* out, int64_t ldo, const float* d_out, int64_t ld_dout, const float* lse,
+                float* delta, float* dq, int64_t lddq, float* dk, int64_t lddk, float* dv, int64_t lddv, void* stream);
+
+/* y = LN(x + r) over the last axis of [m, n] (row strides), r nullable; no affine parameters (net.py:286-290: the
+ * scale 1 / bias 0 that paddle.static.nn.layer_norm creates afresh on every dygraph call), biased variance, rstd =
+ * 1 / sqrt(var + eps).  mean, rstd [m] are saved.  y may be x or r.  y_group > 0: row i of y sits at (i / y_group) *
+ * ldy_group + (i % y_group) * ldy (the encoder output written to rows 1.. of each sample of the tower input).
+ * rec_add_layer_norm_bwd: dx = rstd (dy - mean(dy) - y mean(dy y)) — the gradient of the SUM, which feeds both x and r;
+ * dx may be dy, not y. */
+int rec_add_layer_norm_fwd(int64_t m, int32_t n, const float* x, int64_t ldx, const float* r, int64_t ldr, float eps, float* y,
+                           int64_t ldy, int64_t y_group, int64_t ldy_group, float* mean, float* rstd, void* stream);
+int rec_add_layer_norm_bwd(int64_t m, int32_t n, const float* y, int64_t ldy, int64_t y_group, int64_t ldy_group,
+                           const float* rstd, const float* dy, int64_t lddy, float* dx, int64_t lddx, void* stream);
+
+/* paddle.nn.LeakyReLU: y = x > 0 ? x : slope x over [m, n] (row strides, in place allowed).  The backward reads the
+ * OUTPUT: dx = y > 0 ? dy : slope dy (slope > 0: y has x's sign; at +-0 the gradient is the slope).  dx may be dy. */
+int rec_leaky_relu_fwd(int64_t m, int32_t n, const float* x, int64_t ldx, float slope, float* y, int64_t ldy, void* stream);
+int rec_leaky_relu_bwd(int64_t m, int32_t n, const float* y, int64_t ldy, const float* dy, int64_t lddy, float slope, float* dx,
+                       int64_t lddx, void* stream);
+
+/* BST's glue.
+ * rec_bst_add: y = x + r over [m, n] (row strides; r nullable: a strided copy; in place allowed).
+ * rec_bst_embed_fwd: the seven lookups of net.py:421-442.  ids / id_ld / tables / table_rows: 7 entries in the order
+ *   hist item, hist cat, hist position ([batch, steps] ids, row stride id_ld), target item, target cat, target position,
+ *   user ([batch] ids, element stride id_ld); tables are contiguous [rows, width], widths = {item, cat, position},
+ *   d_model = their sum = the user table's width.  X[(b*(steps+1) + l)*ldx + :] = [item | cat | position] of position l
+ *   (l = steps: the target);  user_out[b*ld_user + :] = user[uid[b]].  An id outside its table reads as a zero row and
+ *   raises REC_FLAG_INDEX_OOB.
+ * rec_bst_embed_bwd: dX [batch*(steps+1), d_model] -> grads[0..2] [batch*steps, width], grads[3..5] [batch, width], the
+ *   contiguous gradient rows of the six sequence lookups.
+ * rec_bst_possum_fwd: y[b] = sum_l z[b*positions + l] + bias[0] (net.py:456, 74).
+ * rec_bst_possum_bwd: dz[b*positions + l] = dy[b];  dbias[0] = sum_b dy[b]. */
+int rec_bst_add(int64_t m, int64_t n, const float* x, int64_t ldx, const float* r, int64_t ldr, float* y, int64_t ldy,
+                void* stream);
+int rec_bst_embed_fwd(int64_t batch, int32_t steps, const int64_t* const* ids, const int64_t* id_ld,
+                      const float* const* tables, const int64_t* table_rows, const int32_t* widths, float* X, int64_t ldx,
+                      float* user_out, int64_t ld_user, int32_t* status, void* stream);
+int rec_bst_embed_bwd(int64_t batch, int32_t steps, const int32_t* widths, const float* dX, int64_t lddx, float* const* grads,
+                      void* stream);
+int rec_bst_possum_fwd(int64_t batch, int32_t positions, const float* z, const float* bias, float* y, void* stream);
+int rec_bst_possum_bwd(int64_t batch, int32_t positions, const float* dy, float* dz, float* dbias, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -280,6 +280,20 @@ SIGNATURES = {
     "rec_dmr_tail_bwd_match": (C.c_int, [_I64, _I32, _P, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _P, _P, _P, _I64, _P]),
     "rec_dmr_tail_bwd_hist": (C.c_int, [_I64, _I32, _I32, _P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P,
                                         _I64, _P, _I64, _P, _I64, _P]),
+    "rec_mha_fwd": (C.c_int, [_I64, _I32, _I32, _I32, _I32, _P, _I64, _P, _I64, _P, _I64, _F, _F, C.c_uint64, C.c_uint64, _P,
+                              _I64, _P, _P]),
+    "rec_mha_bwd": (C.c_int, [_I64, _I32, _I32, _I32, _I32, _P, _I64, _P, _I64, _P, _I64, _F, _F, C.c_uint64, C.c_uint64, _P,
+                              _I64, _P, _I64, _P, _P, _P, _I64, _P, _I64, _P, _I64, _P]),
+    "rec_add_layer_norm_fwd": (C.c_int, [_I64, _I32, _P, _I64, _P, _I64, _F, _P, _I64, _I64, _I64, _P, _P, _P]),
+    "rec_add_layer_norm_bwd": (C.c_int, [_I64, _I32, _P, _I64, _I64, _I64, _P, _P, _I64, _P, _I64, _P]),
+    "rec_leaky_relu_fwd": (C.c_int, [_I64, _I32, _P, _I64, _F, _P, _I64, _P]),
+    "rec_leaky_relu_bwd": (C.c_int, [_I64, _I32, _P, _I64, _P, _I64, _F, _P, _I64, _P]),
+    "rec_bst_add": (C.c_int, [_I64, _I64, _P, _I64, _P, _I64, _P, _I64, _P]),
+    "rec_bst_embed_fwd": (C.c_int, [_I64, _I32, C.POINTER(_P), C.POINTER(_I64), C.POINTER(_P), C.POINTER(_I64),
+                                    C.POINTER(_I32), _P, _I64, _P, _I64, _P, _P]),
+    "rec_bst_embed_bwd": (C.c_int, [_I64, _I32, C.POINTER(_I32), _P, _I64, C.POINTER(_P), _P]),
+    "rec_bst_possum_fwd": (C.c_int, [_I64, _I32, _P, _P, _P, _P]),
+    "rec_bst_possum_bwd": (C.c_int, [_I64, _I32, _P, _P, _P, _P]),
     "rec_dense_fold_fwd": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P]),
     "rec_dense_fold_bwd": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _I32, _P]),
     "rec_dense_fold_fwd_full": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P]),

@@ -2257,6 +2257,211 @@ def dmr_tail_bwd_hist(f1, f2, d_sum, d_prod, item_eb, hist_sum, d_item_direct, d
                                       _stream()), "rec_dmr_tail_bwd_hist")
 
 
+# ------------------------------------------------------------------ BST: attention, add + layer norm, LeakyReLU, glue
+MHA_MAX_L, MHA_MAX_D = 8192, 64
+
+
+def _rows_view(t, name):
+    """A 2-D float32 device view with unit column stride -> its row stride."""
+    _dev(t, torch.float32, name)
+    return _view_ld(t)
+
+
+def _mha_args(q, k, v, B, L, H, what):
+    ldq, ldk, ldv = _rows_view(q, "q"), _rows_view(k, "k"), _rows_view(v, "v")
+    if B < 0 or L < 1 or H < 1 or q.shape[0] != B * L or k.shape != q.shape or v.shape[0] != B * L \
+            or q.shape[1] % H or v.shape[1] % H:
+        raise RecError("%s: q, k must be [B*L, H*d_k] and v [B*L, H*d_v] (B %d, L %d, H %d; got %s, %s, %s)"
+                       % (what, B, L, H, tuple(q.shape), tuple(k.shape), tuple(v.shape)))
+    return q.shape[1] // H, v.shape[1] // H, ldq, ldk, ldv
+
+
+def mha_fwd(q, k, v, B, L, H, scale=1.0, p=0.0, seed=0, stream=0, out=None):
+    """Multi-head attention over [B, L] tokens without an [B,H,L,L] buffer (rec_mha_fwd).  q, k [B*L, H*d_k], v [B*L, H*d_v]:
+    2-D views with a row stride (column ranges of one packed projection output, or separate matrices).  p > 0: dropout on
+    the softmax weights with rec_dropout's keep rule over a virtual [B*H*L, L] matrix.  -> (out [B*L, H*d_v], lse [B,H,L])."""
+    dk, dv, ldq, ldk, ldv = _mha_args(q, k, v, B, L, H, "mha_fwd")
+    if out is None:
+        out = torch.empty(B * L, H * dv, dtype=torch.float32, device=q.device)
+    ldo = _rows_view(out, "out")
+    if tuple(out.shape) != (B * L, H * dv):
+        raise RecError("mha_fwd: out must be [B*L, H*d_v]")
+    lse = torch.empty(B, H, L, dtype=torch.float32, device=q.device)
+    check(lib().rec_mha_fwd(B, L, H, dk, dv, _p(q), ldq, _p(k), ldk, _p(v), ldv, float(scale), float(p), int(seed), int(stream),
+                            _p(out), ldo, _p(lse), _stream()), "rec_mha_fwd")
+    return out, lse
+
+
+def mha_bwd(q, k, v, B, L, H, out, lse, d_out, scale=1.0, p=0.0, seed=0, stream=0, grads=None):
+    """Backward of mha_fwd (the weights are recomputed from lse; `out` is the forward's output).  grads: (dq, dk, dv) views
+    to write (e.g. column ranges of one packed gradient) or None.  -> (dq, dk, dv)."""
+    dk_, dv_, ldq, ldk, ldv = _mha_args(q, k, v, B, L, H, "mha_bwd")
+    _chk(lse, torch.float32, "lse", (B, H, L))
+    if grads is None:
+        grads = (torch.empty(B * L, H * dk_, dtype=torch.float32, device=q.device),
+                 torch.empty(B * L, H * dk_, dtype=torch.float32, device=q.device),
+                 torch.empty(B * L, H * dv_, dtype=torch.float32, device=q.device))
+    dq, dk, dv = grads
+    for t, n, w in ((out, "out", dv_), (d_out, "d_out", dv_), (dq, "dq", dk_), (dk, "dk", dk_), (dv, "dv", dv_)):
+        _rows_view(t, n)
+        if tuple(t.shape) != (B * L, H * w):
+            raise RecError("mha_bwd: %s must be [B*L, %d], got %s" % (n, H * w, tuple(t.shape)))
+    delta = torch.empty(B, H, L, dtype=torch.float32, device=q.device)
+    check(lib().rec_mha_bwd(B, L, H, dk_, dv_, _p(q), ldq, _p(k), ldk, _p(v), ldv, float(scale), float(p), int(seed), int(stream),
+                            _p(out), _view_ld(out), _p(d_out), _view_ld(d_out), _p(lse), _p(delta), _p(dq), _view_ld(dq),
+                            _p(dk), _view_ld(dk), _p(dv), _view_ld(dv), _stream()), "rec_mha_bwd")
+    return dq, dk, dv
+
+
+def _y_group(y, m, n, group):
+    """out=(tensor, group): row i of y is row 1 + i % group of sample i // group of a [B, group + 1, n] tower input."""
+    if group <= 0:
+        return _rows_view(y, "y"), 0, 0
+    _chk(y, torch.float32, "y")
+    if y.dim() != 3 or y.shape[1] != group + 1 or y.shape[2] != n or y.shape[0] * group != m:
+        raise RecError("grouped y must be [m / group, group + 1, n]")
+    return n, group, (group + 1) * n
+
+
+def add_layer_norm_fwd(x, r=None, eps=1e-5, out=None, out_group=0):
+    """y = LN(x + r) over the last axis, no affine parameters, biased variance (rec_add_layer_norm_fwd).  x, r [m, n] views
+    (r may be None); out may be x.  out_group G > 0: out is a [m / G, G + 1, n] tensor whose rows 1.. of every sample are
+    written.  -> (y, mean [m], rstd [m])."""
+    ldx = _rows_view(x, "x")
+    m, n = x.shape
+    if r is not None and (tuple(r.shape) != (m, n)):
+        raise RecError("add_layer_norm_fwd: r must have x's shape")
+    if out is None:
+        out = torch.empty(m, n, dtype=torch.float32, device=x.device)
+    ldy, g, ldg = _y_group(out, m, n, out_group)
+    if not g and tuple(out.shape) != (m, n):
+        raise RecError("add_layer_norm_fwd: out must have x's shape")
+    mean = torch.empty(m, dtype=torch.float32, device=x.device)
+    rstd = torch.empty(m, dtype=torch.float32, device=x.device)
+    yp = C.c_void_p(out.data_ptr() + n * 4) if g else _p(out)            # grouped: row 1 of sample 0
+    check(lib().rec_add_layer_norm_fwd(m, n, _p(x), ldx, _p(r), _rows_view(r, "r") if r is not None else 0, float(eps), yp, ldy,
+                                       g, ldg, _p(mean), _p(rstd), _stream()), "rec_add_layer_norm_fwd")
+    return out, mean, rstd
+
+
+def add_layer_norm_bwd(y, rstd, dy, out=None, y_group=0):
+    """-> dx [m, n] = rstd (dy - mean(dy) - y mean(dy y)): the gradient of x + r (rec_add_layer_norm_bwd).  out may be dy."""
+    lddy = _rows_view(dy, "dy")
+    m, n = dy.shape
+    ldy, g, ldg = _y_group(y, m, n, y_group)
+    _chk(rstd, torch.float32, "rstd", (m,))
+    if out is None:
+        out = torch.empty(m, n, dtype=torch.float32, device=dy.device)
+    if tuple(out.shape) != (m, n) or (not g and tuple(y.shape) != (m, n)):
+        raise RecError("add_layer_norm_bwd: y, dy and out must have one shape")
+    check(lib().rec_add_layer_norm_bwd(m, n, C.c_void_p(y.data_ptr() + n * 4) if g else _p(y), ldy, g, ldg, _p(rstd), _p(dy), lddy, _p(out),
+                                       _rows_view(out, "out"), _stream()), "rec_add_layer_norm_bwd")
+    return out
+
+
+def leaky_relu_fwd(x, slope=0.01, out=None):
+    """paddle.nn.LeakyReLU on a [m, n] view (rec_leaky_relu_fwd); in place by default."""
+    ldx = _rows_view(x, "x")
+    if out is None:
+        out = x
+    if out.shape != x.shape:
+        raise RecError("leaky_relu_fwd: out must have x's shape")
+    check(lib().rec_leaky_relu_fwd(x.shape[0], x.shape[1], _p(x), ldx, float(slope), _p(out), _rows_view(out, "out"), _stream()),
+          "rec_leaky_relu_fwd")
+    return out
+
+
+def leaky_relu_bwd(y, dy, slope=0.01, out=None):
+    """dx = y > 0 ? dy : slope dy, from the OUTPUT y (rec_leaky_relu_bwd); in place on dy by default."""
+    ldy, lddy = _rows_view(y, "y"), _rows_view(dy, "dy")
+    if out is None:
+        out = dy
+    if out.shape != y.shape or dy.shape != y.shape:
+        raise RecError("leaky_relu_bwd: y, dy and out must have one shape")
+    check(lib().rec_leaky_relu_bwd(y.shape[0], y.shape[1], _p(y), ldy, _p(dy), lddy, float(slope), _p(out), _rows_view(out, "out"),
+                                   _stream()), "rec_leaky_relu_bwd")
+    return out
+
+
+def bst_add(x, r=None, out=None):
+    """out = x + r over [m, n] views (r None: a strided copy); in place on x by default (rec_bst_add)."""
+    ldx = _rows_view(x, "x")
+    if out is None:
+        out = x
+    if out.shape != x.shape or (r is not None and r.shape != x.shape):
+        raise RecError("bst_add: x, r and out must have one shape")
+    check(lib().rec_bst_add(x.shape[0], x.shape[1], _p(x), ldx, _p(r), _rows_view(r, "r") if r is not None else 0, _p(out),
+                            _rows_view(out, "out"), _stream()), "rec_bst_add")
+    return out
+
+
+def _bst_widths(tables):
+    w = [int(tables[i].shape[1]) for i in range(3)]
+    if [int(tables[i].shape[1]) for i in range(3, 6)] != w or tables[6].shape[1] != sum(w):
+        raise RecError("bst: the target tables must have the hist tables' widths and the user table their sum")
+    return w
+
+
+def bst_embed_fwd(ids, tables, X, Z, status):
+    """The seven lookups of BST (rec_bst_embed_fwd).  ids: hist item / cat / position [B,T] i64 (strided views are fine),
+    target item / cat / position and user [B] or [B,1] i64; tables: the seven weights in the same order.  X [B*(T+1),
+    d_model] receives [item | cat | position] per position (the target last), Z [B, T+2, d_model] its row 0 = the user row."""
+    B, T = ids[0].shape
+    w = _bst_widths(tables)
+    dm = sum(w)
+    ld = []
+    for i, t in enumerate(ids):
+        _dev(t, torch.int64, "ids[%d]" % i)
+        if i < 3:
+            if tuple(t.shape) != (B, T) or (T > 1 and t.stride(1) != 1):
+                raise RecError("bst_embed_fwd: the history ids must be [B, T] with unit column stride")
+        elif t.numel() != B or t.dim() not in (1, 2):
+            raise RecError("bst_embed_fwd: the target and user ids must be [B] or [B, 1]")
+        ld.append(t.stride(0) if B > 1 else max(T, 1))
+    for i, t in enumerate(tables):
+        _chk(t, torch.float32, "tables[%d]" % i)
+    _chk(X, torch.float32, "X", (B * (T + 1), dm))
+    _chk(Z, torch.float32, "Z", (B, T + 2, dm))
+    check(lib().rec_bst_embed_fwd(B, T, (C.c_void_p * 7)(*[_p(t) for t in ids]), (C.c_int64 * 7)(*ld),
+                                  (C.c_void_p * 7)(*[_p(t) for t in tables]), (C.c_int64 * 7)(*[t.shape[0] for t in tables]),
+                                  (C.c_int32 * 3)(*w), _p(X), dm, _p(Z), (T + 2) * dm, _p(status), _stream()), "rec_bst_embed_fwd")
+
+
+def bst_embed_bwd(dX, B, T, widths):
+    """dX [B*(T+1), d_model] -> the contiguous gradient rows of the six sequence lookups: three [B*T, w], three [B, w]
+    (rec_bst_embed_bwd)."""
+    lddx = _rows_view(dX, "dX")
+    w = [int(x) for x in widths]
+    if tuple(dX.shape) != (B * (T + 1), sum(w)):
+        raise RecError("bst_embed_bwd: dX must be [B*(T+1), d_model]")
+    g = [torch.empty(B * T, x, dtype=torch.float32, device=dX.device) for x in w] + \
+        [torch.empty(B, x, dtype=torch.float32, device=dX.device) for x in w]
+    check(lib().rec_bst_embed_bwd(B, T, (C.c_int32 * 3)(*w), _p(dX), lddx, (C.c_void_p * 6)(*[_p(t) for t in g]), _stream()),
+          "rec_bst_embed_bwd")
+    return g
+
+
+def bst_possum_fwd(z, bias, B):
+    """y [B,1] = sum over the positions of z [B*P, 1] + bias [1] (rec_bst_possum_fwd)."""
+    _chk(z, torch.float32, "z")
+    _chk(bias, torch.float32, "bias", (1,))
+    if B < 0 or (B and z.numel() % B):
+        raise RecError("bst_possum_fwd: z must hold B * P logits")
+    y = torch.empty(B, 1, dtype=torch.float32, device=z.device)
+    check(lib().rec_bst_possum_fwd(B, z.numel() // max(B, 1), _p(z), _p(bias), _p(y), _stream()), "rec_bst_possum_fwd")
+    return y
+
+
+def bst_possum_bwd(dy, P, dbias):
+    """-> dz [B*P, 1] = dy broadcast over the positions; dbias [1] = sum_b dy (rec_bst_possum_bwd)."""
+    _chk(dy, torch.float32, "dy")
+    _chk(dbias, torch.float32, "dbias", (1,))
+    B = dy.numel()
+    dz = torch.empty(B * P, 1, dtype=torch.float32, device=dy.device)
+    check(lib().rec_bst_possum_bwd(B, int(P), _p(dy), _p(dz), _p(dbias), _stream()), "rec_bst_possum_bwd")
+    return dz
+
+
 # ------------------------------------------------------------------ xDeepFM CIN (the passes around the GEMM)
 def _chk_f32(t, name):
     if not t.is_cuda:

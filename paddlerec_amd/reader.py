@@ -544,3 +544,50 @@ class AlimamaReader:
                 sparse = torch.from_numpy(arr.astype(np.int64))
                 price = torch.from_numpy(np.ascontiguousarray(arr[:, self.PRICE_COL:self.PRICE_COL + 1]))
                 yield sparse.to(self.device, non_blocking=True), price.to(self.device, non_blocking=True)
+
+
+class AmazonBSTReader:
+    """models/rank/bst/amazon_reader.py RecDataset with the batching of the other readers (drop_last over the
+    concatenation of the files): lines of `slot:id` tokens for the slots label, userid, history, cate, position, target,
+    target_cate, target_position; tokens of other slots are skipped; a slot missing from a line reads as [0].  history,
+    cate and position are padded with 0 to the longest history found in ALL files of the list (the reference pre-scans the
+    whole list before it yields), so the sequence length is a property of the data set, not of the batch.  Yields the
+    eight int64 arrays of bst/dygraph_model.py:63-73 on `device`: label, userid [B,1], history, cate, position [B,T],
+    target, target_cate, target_position [B,1]."""
+    SLOTS = ("label", "userid", "history", "cate", "position", "target", "target_cate", "target_position")
+    PADDED = (2, 3, 4)
+
+    def __init__(self, file_list, batch_size, device="cuda"):
+        self.file_list, self.batch_size, self.device = list(file_list), int(batch_size), device
+
+    def max_len(self):
+        """The longest history of the file list (amazon_reader.py:46-56)."""
+        longest = 0
+        for path in self.file_list:
+            with open(path, "r") as f:
+                for line in f:
+                    longest = max(longest, sum(1 for tok in line.strip().split(" ") if tok.split(":")[0] == "history"))
+        return longest
+
+    def _rows(self, max_len):
+        index = {s: i for i, s in enumerate(self.SLOTS)}
+        for path in self.file_list:
+            with open(path, "r") as f:
+                for line in f:
+                    out = [[] for _ in self.SLOTS]
+                    for tok in line.strip().split(" "):
+                        parts = tok.split(":")
+                        if parts[0] in index:
+                            out[index[parts[0]]].append(int(parts[1]))
+                    out = [v or [0] for v in out]
+                    yield [np.asarray(v + [0] * (max_len - len(v)) if i in self.PADDED else v, np.int64)
+                           for i, v in enumerate(out)]
+
+    def __iter__(self):
+        group = []
+        for row in self._rows(self.max_len()):
+            group.append(row)
+            if len(group) == self.batch_size:
+                arrs = [np.stack([r[i] for r in group]) for i in range(len(self.SLOTS))]
+                group = []
+                yield tuple(torch.from_numpy(a).to(self.device, non_blocking=True) for a in arrs)

@@ -10,7 +10,7 @@ What differs by construction: a batch never becomes 28 per-sample NumPy arrays (
 [B,26] / [B,13] device tensors), `loss.backward(); optimizer.step()` is the explicit `train_step` chain of the
 host mirrors, and the AUC buckets stay on the device (read back only when a log line prints them).
 
-    python -m paddlerec_amd.trainer -m <config.yaml> [--model deepfm|fm|ffm|deepfefm|fat_deepffm|wide_deep|dnn|dcn|dcn_v2|gatenet|flen|autofis|din|dien|dmr|xdeepfm|dlrm] [-o runner.epochs=1 ...] [--infer]
+    python -m paddlerec_amd.trainer -m <config.yaml> [--model deepfm|fm|ffm|deepfefm|fat_deepffm|wide_deep|dnn|dcn|dcn_v2|gatenet|flen|autofis|din|dien|dmr|bst|xdeepfm|dlrm] [-o runner.epochs=1 ...] [--infer]
     python -m torch.distributed.run --nproc-per-node G -m paddlerec_amd.trainer -m <config.yaml>     # collective mode
 """
 import argparse
@@ -25,7 +25,7 @@ from . import checkpoint
 logger = logging.getLogger("paddlerec_amd.trainer")
 
 MODELS = ("deepfm", "fm", "ffm", "deepfefm", "fat_deepffm", "wide_deep", "dnn", "dcn", "dcn_v2", "gatenet", "flen", "autofis",
-          "din", "dien", "dmr", "xdeepfm", "dlrm")
+          "din", "dien", "dmr", "bst", "xdeepfm", "dlrm")
 
 
 # ------------------------------------------------------------------------------------ configuration
@@ -102,6 +102,8 @@ def _dygraph_model(name):
         from .dien import DygraphModel
     elif name == "dmr":
         from .dmr import DygraphModel
+    elif name == "bst":
+        from .bst import DygraphModel
     elif name == "xdeepfm":
         from .xdeepfm import DygraphModel
     elif name == "dlrm":
@@ -138,6 +140,8 @@ def create_data_loader(config, model, device, mode="train", shard=None):
         return lambda: iter(rd)                       # ONE reader: its negative-candidate pools carry across epochs
     if model == "dmr":
         return lambda: iter(reader.AlimamaReader(files, bs, device))
+    if model == "bst":
+        return lambda: iter(reader.AmazonBSTReader(files, bs, device))
     if model == "flen":
         return lambda: iter(reader.AvazuReader(files, bs, device, shard=shard))
     if model == "autofis":
@@ -298,6 +302,11 @@ def _apply_optimizer_config(config, model, dy_model):
         from .dmr import QUIRKS
         logger.info("dmr, kept as the reference writes it: %s; Adam (non-lazy, every row of every table moves) at the "
                     "YAML's learning rate", QUIRKS)
+    if model == "bst":
+        from .bst import QUIRKS
+        logger.info("bst, kept as the reference writes it: %s; preprocess_cmd=%r postprocess_cmd=%r, Dropout(%.2f) with "
+                    "the engine's counter-based masks (seed %d)", QUIRKS, dy_model.preprocess_cmd, dy_model.postprocess_cmd,
+                    dy_model.dropout_rate, dy_model.dropout_seed)
     if model == "dcn_v2":
         logger.info("dcn_v2 train mode: Dropout(%.2f) after every element of the DNN tower (dcn_v2/net.py:181-183) with the "
                     "engine's counter-based masks (seed %d; Paddle's own mask stream is not reproducible), L2Decay(%g) on "
