@@ -582,7 +582,8 @@ int rec_din_attention_pool_fwd(const rec_din_desc* desc, const int64_t* hist_ite
                                const float* att_b2, const float* att_w3, const float* att_b3,
                                float* out, float* att_weight, float* act1, int32_t* status, void* stream);
 /* The same forward with a caller-owned workspace (rec_din_attention_pool_fwd_workspace_bytes; 0 bytes = the shape
- * never needs one).  With it, a batch of FEW samples (the reference's din/config.yaml batch size 32: fewer samples than
+ * never needs one; when the query is not 0, a missing or smaller workspace is REC_EWORKSPACE before any launch — a caller
+ * without a workspace calls rec_din_attention_pool_fwd).  With it, a batch of FEW samples (the reference's din/config.yaml batch size 32: fewer samples than
  * the chip has block slots) is computed one block per 32-position history tile — each tile softmax-normalised on its
  * own, a second launch rescales the pieces to the softmax over the whole history — instead of one block per sample
  * walking its tiles one after the other (82 -> ~25 us at 32 x 152).  Same results up to fp32 rounding of the
@@ -618,7 +619,8 @@ int rec_din_attention_pool_bwd(const rec_din_desc* desc, const int64_t* hist_ite
                                const float* d_out, float* d_hist, float* d_tgt_seq, void* stream);
 
 /* The same backward with a caller-owned workspace (rec_din_attention_pool_bwd_workspace_bytes; 0 bytes = the shape never
- * needs one): at batches larger than the resident grid the blocks of the saved-activation kernel draw their next SAMPLE
+ * needs one; otherwise a missing or smaller workspace is REC_EWORKSPACE before any launch, and a caller without one
+ * calls rec_din_attention_pool_bwd): at batches larger than the resident grid the blocks of the saved-activation kernel draw their next SAMPLE
  * from a ticket counter in it instead of walking fixed ranges — samples cost between one and max_len / 32 tiles once
  * tiles whose saved weights are all zero are skipped.  Same results: which block computes a tile changes nothing. */
 int rec_din_attention_pool_bwd_workspace_bytes(const rec_din_desc* desc, size_t* bytes);
@@ -753,6 +755,8 @@ int rec_accuracy_count(int64_t n, const float* pred, const int64_t* label, int64
  *   WORKSPACE: under (b) a forward / dX call WRITES op(B)'s three-plane image into the workspace (unless
  *   rec_gemm_epilogue_args.b_image hands one in) and a weight-gradient call its partial tiles — so, unlike (a) without
  *   split-K, concurrent calls on two streams need one workspace each.  rec_gemm_f32_workspace_bytes covers both families.
+ *   A call that takes a kernel of (b) is held to that figure: with fewer bytes than its image (forward / dX, no b_image) or
+ *   its partial tiles (weight gradient) need it fails with REC_EWORKSPACE before any launch; it does not change family.
  * ---------------------------------------------------------------------------------------- */
 typedef enum {
   REC_EPI_NONE = 0,
@@ -826,6 +830,8 @@ int rec_gemm_f32(const rec_gemm_desc* desc, const float* A, const float* B, floa
  * reference's own batch sizes both are launch-bound (M N K < 1.5e8, K <= 1024: csrc/gemm_direct.h) and go out as ONE
  * launch whose workgroups run exactly the code of the single launches — bit-identical to two rec_gemm_f32 calls, one
  * ~4 us launch less; any other pair IS two rec_gemm_f32 calls, desc0 first (workspace: the larger of the two needs).
+ * The call checks the workspace against the larger of the two rec_gemm_f32_workspace_bytes figures before EITHER GEMM is
+ * launched (REC_EWORKSPACE: neither C0 nor C1 has been written).
  * REC_GEMM_PAIR=0: always two calls. */
 int rec_gemm_f32_pair(const rec_gemm_desc* desc0, const float* A0, const float* B0, float* C0,
                       const rec_gemm_epilogue_args* args0 /* may be NULL */, const rec_gemm_desc* desc1, const float* A1,
@@ -1453,7 +1459,7 @@ typedef struct {
 } rec_dcn_cross_desc;
 
 /* Bytes of `workspace` for one shape: the backward's per-block partials of d_w / d_b; the forward's per-block l2
- * partials fit in the same figure. */
+ * partials fit in the same figure.  Both calls hold the caller to this ONE figure: fewer bytes are REC_EWORKSPACE. */
 int rec_dcn_cross_bwd_workspace_bytes(const rec_dcn_cross_desc* desc, size_t* bytes);
 /* X0 [B,ld_x0]; w, b [d] -> XL [B,ld_out] = x_L;  saved [B,L] = s_l[r] at r*L + l, or NULL;  l2_out [1] or NULL.
  * Inference passes saved = l2_out = NULL: nothing is stored or summed for them and no workspace is needed.  With l2_out
@@ -1486,7 +1492,8 @@ int rec_dcn_cross_bwd(const rec_dcn_cross_desc* desc, const float* X0, const flo
 int rec_gate_emb_fwd(int64_t n, int32_t num_fields, int32_t emb_dim, int32_t row_stride, int64_t num_rows,
                      int64_t padding_idx, const int64_t* ids, const float* W, const float* gate_w, float* out,
                      int64_t out_stride, int32_t* status, void* stream);
-/* Bytes of `workspace` for rec_gate_emb_bwd: its per-block partials of d_gate_w (at most 2048 blocks of num_fields). */
+/* Bytes of `workspace` for rec_gate_emb_bwd: its per-block partials of d_gate_w (at most 2048 blocks of num_fields).
+ * The call holds the caller to this figure whatever lane shape runs: fewer bytes are REC_EWORKSPACE before any launch. */
 int rec_gate_emb_bwd_workspace_bytes(int64_t n, int32_t num_fields, size_t* bytes);
 /* Backward of the gate, IN PLACE on g (the layout of `out` above, stride g_stride): on entry g = dloss / d out, on
  * return g = dloss / d e.  e is gathered again from W (not yet updated), t and a are recomputed:

@@ -327,12 +327,15 @@ extern "C" int rec_dcn_cross_fwd(const rec_dcn_cross_desc* desc, const float* X0
               desc->d);
   const int grid = dcn_fwd_grid(desc->batch);
   if (l2_out) {
-    const size_t need = (size_t)grid * sizeof(float);
-    REC_REQUIRE(workspace_bytes >= need, REC_EWORKSPACE, "dcn cross fwd workspace %zu < %zu bytes", workspace_bytes, need);
+    size_t need = 0;                                  // the ONE figure of the query, as the backward: a caller sizes once
+    rec_dcn_cross_bwd_workspace_bytes(desc, &need);
+    REC_REQUIRE(workspace_bytes >= need, REC_EWORKSPACE,
+                "dcn cross fwd workspace %zu < %zu bytes", workspace_bytes, need);
+    REC_REQUIRE(workspace || need == 0, REC_EINVAL, "null pointer argument");
   }
   if (desc->batch == 0) return REC_OK;
   hipStream_t st = (hipStream_t)stream;
-  REC_REQUIRE(X0 && w && b && XL && (!l2_out || workspace), REC_EINVAL, "null pointer argument");
+  REC_REQUIRE(X0 && w && b && XL, REC_EINVAL, "null pointer argument");
   const DcnArgs a = dcn_args(desc);
   float* part = l2_out ? (float*)workspace : nullptr;
   const bool vec = dcn_vec_ok(X0, a.ld_x0) && dcn_vec_ok(XL, a.ld_out);
@@ -363,11 +366,14 @@ extern "C" int rec_dcn_cross_bwd(const rec_dcn_cross_desc* desc, const float* X0
   REC_REQUIRE(rank1 || desc->ld_dxl >= desc->d, REC_EINVAL, "dcn cross: row stride ld_dxl %lld < d %d",
               (long long)desc->ld_dxl, desc->d);
   const int grid = dcn_bwd_grid(desc->batch, desc->d);
-  const size_t need = (size_t)grid * 2 * (size_t)desc->d * sizeof(float);
-  REC_REQUIRE(workspace_bytes >= need, REC_EWORKSPACE, "dcn cross bwd workspace %zu < %zu bytes", workspace_bytes, need);
+  size_t need = 0;                                    // the query's figure (it also covers the forward's partials)
+  rec_dcn_cross_bwd_workspace_bytes(desc, &need);
+  REC_REQUIRE(workspace_bytes >= need, REC_EWORKSPACE,
+              "dcn cross bwd workspace %zu < %zu bytes", workspace_bytes, need);
+  REC_REQUIRE(workspace || need == 0, REC_EINVAL, "null pointer argument");
   if (desc->batch == 0) return REC_OK;
   hipStream_t st = (hipStream_t)stream;
-  REC_REQUIRE(X0 && w && b && saved && (dXL || rank1) && dX0 && d_w && d_b && workspace, REC_EINVAL,
+  REC_REQUIRE(X0 && w && b && saved && (dXL || rank1) && dX0 && d_w && d_b, REC_EINVAL,
               "null pointer argument");
   const DcnArgs a = dcn_args(desc);
   float* part = (float*)workspace;

@@ -538,10 +538,11 @@ extern "C" int rec_dien_aux_fwd(int64_t batch, int32_t steps, int32_t item_dim, 
   const int64_t n = batch * steps;
   hipStream_t st = (hipStream_t)stream;
   if (n > 0) {
-    REC_REQUIRE(gru_out && hist && neg_item && neg_cat && W_neg_item && W_neg_cat && status && workspace, REC_EINVAL,
+    REC_REQUIRE(gru_out && hist && neg_item && neg_cat && W_neg_item && W_neg_cat && status, REC_EINVAL,
                 "null pointer argument");
     REC_REQUIRE(workspace_bytes >= (size_t)n * sizeof(float), REC_EWORKSPACE, "dien aux workspace %zu < %zu bytes",
                 workspace_bytes, (size_t)n * sizeof(float));
+    REC_REQUIRE(workspace, REC_EINVAL, "null pointer argument");
     const AuxArgs a{n, steps, item_dim + cat_dim, item_dim, gru_out, hist, neg_item, neg_cat, W_neg_item, item_stride,
                     item_rows, W_neg_cat, cat_stride, cat_rows, padding_idx, status};
     hipLaunchKernelGGL(dien_aux_fwd_kernel, dim3((unsigned)((n + 3) / 4)), dim3(kBlock), 0, st, a, (float*)workspace);

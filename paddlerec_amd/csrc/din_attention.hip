@@ -1538,16 +1538,14 @@ bool rec::din_combine_rider_take() {
   return taken;
 }
 
-extern "C" int rec_din_attention_pool_fwd_ws(const rec_din_desc* d, const int64_t* hist_item,
-                                          const int64_t* hist_cat, const int64_t* tgt_item_seq,
-                                          const int64_t* tgt_cat_seq, const int64_t* mask,
-                                          const float* w_hist_item, const float* w_hist_cat,
-                                          const float* w_tgt_item_seq, const float* w_tgt_cat_seq,
-                                          const float* att_w1, const float* att_b1,
-                                          const float* att_w2, const float* att_b2,
-                                          const float* att_w3, const float* att_b3, float* out,
-                                          float* att_weight, float* act1, int32_t* status, void* workspace,
-                                          size_t workspace_bytes, void* stream) {
+// own_ws: the caller came through the _ws entry point and owes the workspace its query names (REC_EWORKSPACE otherwise);
+// the entry point without a workspace passes (nullptr, 0) and false.
+static int din_fwd_run(const rec_din_desc* d, const int64_t* hist_item, const int64_t* hist_cat, const int64_t* tgt_item_seq,
+                       const int64_t* tgt_cat_seq, const int64_t* mask, const float* w_hist_item, const float* w_hist_cat,
+                       const float* w_tgt_item_seq, const float* w_tgt_cat_seq, const float* att_w1, const float* att_b1,
+                       const float* att_w2, const float* att_b2, const float* att_w3, const float* att_b3, float* out,
+                       float* att_weight, float* act1, int32_t* status, void* workspace, size_t workspace_bytes, bool own_ws,
+                       void* stream) {
   REC_REQUIRE(d, REC_EINVAL, "desc is NULL");
   const int E = d->item_dim + d->cat_dim;
   REC_REQUIRE(d->batch >= 0 && d->max_len > 0 && d->item_dim > 0 && d->cat_dim > 0 && d->hidden1 > 0 &&
@@ -1565,6 +1563,12 @@ extern "C" int rec_din_attention_pool_fwd_ws(const rec_din_desc* d, const int64_
   REC_REQUIRE(hist_item && hist_cat && tgt_item_seq && tgt_cat_seq && mask && w_hist_item && w_hist_cat &&
                   w_tgt_item_seq && w_tgt_cat_seq && att_w1 && att_b1 && att_w2 && att_b2 && att_w3 &&
                   att_b3 && out && status, REC_EINVAL, "null pointer argument");
+  if (own_ws) {
+    size_t owed = 0;
+    rec_din_attention_pool_fwd_workspace_bytes(d, &owed);
+    REC_REQUIRE(owed == 0 || (workspace && workspace_bytes >= owed), REC_EWORKSPACE, "workspace %zu < %zu", workspace_bytes,
+                owed);
+  }
   const int H1 = d->hidden1, H2 = d->hidden2;
   size_t shmem = sizeof(float) * ((size_t)2 * kDinTP * (E + 4) + (size_t)kDinTP * (H1 + H2) +
                                   (size_t)H1 * H2 + 2 * H2 + H1 + (size_t)d->max_len);
@@ -1654,25 +1658,24 @@ extern "C" int rec_din_attention_pool_fwd(const rec_din_desc* d, const int64_t* 
                                           const float* att_w2, const float* att_b2,
                                           const float* att_w3, const float* att_b3, float* out,
                                           float* att_weight, float* act1, int32_t* status, void* stream) {
-  return rec_din_attention_pool_fwd_ws(d, hist_item, hist_cat, tgt_item_seq, tgt_cat_seq, mask, w_hist_item, w_hist_cat,
-                                       w_tgt_item_seq, w_tgt_cat_seq, att_w1, att_b1, att_w2, att_b2, att_w3, att_b3, out,
-                                       att_weight, act1, status, nullptr, 0, stream);
+  return din_fwd_run(d, hist_item, hist_cat, tgt_item_seq, tgt_cat_seq, mask, w_hist_item, w_hist_cat, w_tgt_item_seq,
+                     w_tgt_cat_seq, att_w1, att_b1, att_w2, att_b2, att_w3, att_b3, out, att_weight, act1, status, nullptr, 0,
+                     false, stream);
 }
 
-extern "C" int rec_din_attention_pool_bwd(const rec_din_desc* d, const int64_t* hist_item,
-                                          const int64_t* hist_cat, const int64_t* tgt_item_seq,
-                                          const int64_t* tgt_cat_seq, const float* w_hist_item,
-                                          const float* w_hist_cat, const float* w_tgt_item_seq,
-                                          const float* w_tgt_cat_seq, const float* att_w1,
-                                          const float* att_w1_t, const float* att_b1,
-                                          const float* att_w2, const float* att_b2,
-                                          const float* att_w3, const float* att_weight,
-                                          const float* out_saved, const float* act1_saved,
-                                          const float* d_out, float* d_hist, float* d_tgt_seq,
-                                          void* stream) {
-  return rec_din_attention_pool_bwd_ws(d, hist_item, hist_cat, tgt_item_seq, tgt_cat_seq, w_hist_item, w_hist_cat,
-                                       w_tgt_item_seq, w_tgt_cat_seq, att_w1, att_w1_t, att_b1, att_w2, att_b2, att_w3,
-                                       att_weight, out_saved, act1_saved, d_out, d_hist, d_tgt_seq, nullptr, 0, stream);
+extern "C" int rec_din_attention_pool_fwd_ws(const rec_din_desc* d, const int64_t* hist_item,
+                                             const int64_t* hist_cat, const int64_t* tgt_item_seq,
+                                             const int64_t* tgt_cat_seq, const int64_t* mask,
+                                             const float* w_hist_item, const float* w_hist_cat,
+                                             const float* w_tgt_item_seq, const float* w_tgt_cat_seq,
+                                             const float* att_w1, const float* att_b1,
+                                             const float* att_w2, const float* att_b2,
+                                             const float* att_w3, const float* att_b3, float* out,
+                                             float* att_weight, float* act1, int32_t* status, void* workspace,
+                                             size_t workspace_bytes, void* stream) {
+  return din_fwd_run(d, hist_item, hist_cat, tgt_item_seq, tgt_cat_seq, mask, w_hist_item, w_hist_cat, w_tgt_item_seq,
+                     w_tgt_cat_seq, att_w1, att_b1, att_w2, att_b2, att_w3, att_b3, out, att_weight, act1, status, workspace,
+                     workspace_bytes, true, stream);
 }
 
 // one 32-bit ticket counter for the compile-time-shaped kernel at batches larger than the resident grid; else nothing
@@ -1682,17 +1685,13 @@ extern "C" int rec_din_attention_pool_bwd_workspace_bytes(const rec_din_desc* d,
   return REC_OK;
 }
 
-extern "C" int rec_din_attention_pool_bwd_ws(const rec_din_desc* d, const int64_t* hist_item,
-                                             const int64_t* hist_cat, const int64_t* tgt_item_seq,
-                                             const int64_t* tgt_cat_seq, const float* w_hist_item,
-                                             const float* w_hist_cat, const float* w_tgt_item_seq,
-                                             const float* w_tgt_cat_seq, const float* att_w1,
-                                             const float* att_w1_t, const float* att_b1,
-                                             const float* att_w2, const float* att_b2,
-                                             const float* att_w3, const float* att_weight,
-                                             const float* out_saved, const float* act1_saved,
-                                             const float* d_out, float* d_hist, float* d_tgt_seq,
-                                             void* workspace, size_t workspace_bytes, void* stream) {
+// own_ws: as din_fwd_run
+static int din_bwd_run(const rec_din_desc* d, const int64_t* hist_item, const int64_t* hist_cat, const int64_t* tgt_item_seq,
+                       const int64_t* tgt_cat_seq, const float* w_hist_item, const float* w_hist_cat,
+                       const float* w_tgt_item_seq, const float* w_tgt_cat_seq, const float* att_w1, const float* att_w1_t,
+                       const float* att_b1, const float* att_w2, const float* att_b2, const float* att_w3,
+                       const float* att_weight, const float* out_saved, const float* act1_saved, const float* d_out,
+                       float* d_hist, float* d_tgt_seq, void* workspace, size_t workspace_bytes, bool own_ws, void* stream) {
   REC_REQUIRE(d, REC_EINVAL, "desc is NULL");
   const int E = d->item_dim + d->cat_dim;
   REC_REQUIRE(d->batch >= 0 && d->max_len > 0 && d->item_dim > 0 && d->cat_dim > 0 && d->hidden1 > 0 &&
@@ -1707,6 +1706,12 @@ extern "C" int rec_din_attention_pool_bwd_ws(const rec_din_desc* d, const int64_
   REC_REQUIRE(hist_item && hist_cat && tgt_item_seq && tgt_cat_seq && w_hist_item && w_hist_cat &&
                   w_tgt_item_seq && w_tgt_cat_seq && att_w1 && att_w1_t && att_b1 && att_w2 && att_b2 &&
                   att_w3 && att_weight && d_out && d_hist && d_tgt_seq, REC_EINVAL, "null pointer argument");
+  if (own_ws) {
+    size_t owed = 0;
+    rec_din_attention_pool_bwd_workspace_bytes(d, &owed);
+    REC_REQUIRE(owed == 0 || (workspace && workspace_bytes >= owed), REC_EWORKSPACE, "workspace %zu < %zu", workspace_bytes,
+                owed);
+  }
   const int H1 = d->hidden1, H2 = d->hidden2;
   const size_t shmem = sizeof(float) * ((size_t)2 * kDinTP * E + (size_t)kDinTP * (H1 + H2) + (size_t)H1 * H2 +
                                         2 * H2 + H1 + kDinTP + kBlock / kWave + (size_t)d->max_len);
@@ -1750,3 +1755,37 @@ extern "C" int rec_din_attention_pool_bwd_ws(const rec_din_desc* d, const int64_
                      (hipStream_t)stream, g);
   return check_launch("rec_din_attention_pool_bwd");
 }
+
+extern "C" int rec_din_attention_pool_bwd(const rec_din_desc* d, const int64_t* hist_item,
+                                          const int64_t* hist_cat, const int64_t* tgt_item_seq,
+                                          const int64_t* tgt_cat_seq, const float* w_hist_item,
+                                          const float* w_hist_cat, const float* w_tgt_item_seq,
+                                          const float* w_tgt_cat_seq, const float* att_w1,
+                                          const float* att_w1_t, const float* att_b1,
+                                          const float* att_w2, const float* att_b2,
+                                          const float* att_w3, const float* att_weight,
+                                          const float* out_saved, const float* act1_saved,
+                                          const float* d_out, float* d_hist, float* d_tgt_seq,
+                                          void* stream) {
+  return din_bwd_run(d, hist_item, hist_cat, tgt_item_seq, tgt_cat_seq, w_hist_item, w_hist_cat, w_tgt_item_seq,
+                     w_tgt_cat_seq, att_w1, att_w1_t, att_b1, att_w2, att_b2, att_w3, att_weight, out_saved, act1_saved, d_out,
+                     d_hist, d_tgt_seq, nullptr, 0, false, stream);
+}
+
+
+extern "C" int rec_din_attention_pool_bwd_ws(const rec_din_desc* d, const int64_t* hist_item,
+                                             const int64_t* hist_cat, const int64_t* tgt_item_seq,
+                                             const int64_t* tgt_cat_seq, const float* w_hist_item,
+                                             const float* w_hist_cat, const float* w_tgt_item_seq,
+                                             const float* w_tgt_cat_seq, const float* att_w1,
+                                             const float* att_w1_t, const float* att_b1,
+                                             const float* att_w2, const float* att_b2,
+                                             const float* att_w3, const float* att_weight,
+                                             const float* out_saved, const float* act1_saved,
+                                             const float* d_out, float* d_hist, float* d_tgt_seq,
+                                             void* workspace, size_t workspace_bytes, void* stream) {
+  return din_bwd_run(d, hist_item, hist_cat, tgt_item_seq, tgt_cat_seq, w_hist_item, w_hist_cat, w_tgt_item_seq,
+                     w_tgt_cat_seq, att_w1, att_w1_t, att_b1, att_w2, att_b2, att_w3, att_weight, out_saved, act1_saved, d_out,
+                     d_hist, d_tgt_seq, workspace, workspace_bytes, true, stream);
+}
+

@@ -670,11 +670,12 @@ extern "C" int rec_prelu_bwd(int64_t m, int32_t n, const float* X, int64_t ldx, 
   const int64_t nblk = (s.mv + kPreluRows - 1) / kPreluRows;
   hipStream_t st = (hipStream_t)stream;
   if (m > 0) {
-    REC_REQUIRE(X && dY && dX && workspace, REC_EINVAL, "null pointer argument");
+    REC_REQUIRE(X && dY && dX, REC_EINVAL, "null pointer argument");
     REC_REQUIRE(ldx >= n && lddy >= n && lddx >= n, REC_EINVAL, "rec_prelu_bwd: a row stride is smaller than n");
     REC_REQUIRE(dX != X, REC_EINVAL, "rec_prelu_bwd: dX must not be X");
     const size_t need = (size_t)nblk * (size_t)s.nv * sizeof(float);
     REC_REQUIRE(workspace_bytes >= need, REC_EWORKSPACE, "prelu workspace %zu < %zu bytes", workspace_bytes, need);
+    REC_REQUIRE(workspace, REC_EINVAL, "null pointer argument");
     const dim3 grid((unsigned)((s.nv + kBlock - 1) / kBlock), (unsigned)nblk);
     hipLaunchKernelGGL(prelu_bwd_kernel, grid, dim3(kBlock), 0, st, s, X, ldx, dY, lddy, alpha, dX, lddx,
                        (float*)workspace);
@@ -708,10 +709,11 @@ extern "C" int rec_dmr_match_loss_fwd(int64_t batch, int64_t classes, int32_t k,
   hipStream_t st = (hipStream_t)stream;
   float* term = nullptr;
   if (batch > 0) {
-    REC_REQUIRE(label && lse && status && workspace, REC_EINVAL, "null pointer argument");
+    REC_REQUIRE(label && lse && status, REC_EINVAL, "null pointer argument");
     REC_REQUIRE(ld_label >= 1, REC_EINVAL, "rec_dmr_match_loss_fwd: ld_label must be >= 1");
     REC_REQUIRE(workspace_bytes >= match_fwd_bytes(batch), REC_EWORKSPACE, "dmr match loss workspace %zu < %zu bytes",
                 workspace_bytes, match_fwd_bytes(batch));
+    REC_REQUIRE(workspace, REC_EINVAL, "null pointer argument");
     float* pm = (float*)workspace;
     float* ps = pm + batch * kMatchChunks;
     float* lab = ps + batch * kMatchChunks;
@@ -748,12 +750,13 @@ extern "C" int rec_dmr_match_loss_bwd(int64_t batch, int64_t classes, int32_t k,
   const int64_t cgrid = (classes * k + kBlock - 1) / kBlock;
   REC_REQUIRE(cgrid < (1ll << 31), REC_ESHAPE, "rec_dmr_match_loss_bwd: classes * k too large");
   if (batch > 0) {
-    REC_REQUIRE(label && lse && dU && workspace, REC_EINVAL, "null pointer argument");
+    REC_REQUIRE(label && lse && dU, REC_EINVAL, "null pointer argument");
     REC_REQUIRE(ld_label >= 1 && lddu >= k, REC_EINVAL, "rec_dmr_match_loss_bwd: a stride is smaller than its row");
     REC_REQUIRE(dU != U, REC_EINVAL, "rec_dmr_match_loss_bwd: dU must not be U");
-    REC_REQUIRE(((uintptr_t)workspace) % 16 == 0, REC_EINVAL, "rec_dmr_match_loss_bwd: workspace must be 16-byte aligned");
     const size_t need = match_bwd_bytes(batch, classes, k);
     REC_REQUIRE(workspace_bytes >= need, REC_EWORKSPACE, "dmr match loss workspace %zu < %zu bytes", workspace_bytes, need);
+    REC_REQUIRE(workspace, REC_EINVAL, "null pointer argument");
+    REC_REQUIRE(((uintptr_t)workspace) % 16 == 0, REC_EINVAL, "rec_dmr_match_loss_bwd: workspace must be 16-byte aligned");
     const float scale = d_loss / (float)batch;
     float* part = (float*)workspace;
     MatchArgs a{batch, classes, k / 4, U, ldu, V, ldv, bias, label, ld_label, p.chunk, p.nch};

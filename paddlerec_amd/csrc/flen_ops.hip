@@ -342,11 +342,12 @@ extern "C" int rec_flen_bwd(int64_t batch, int32_t num_slots, int32_t num_groups
     hipLaunchKernelGGL(flen_fold_kernel, dim3(1), dim3(kBlock), 0, st, 0, P, (const float*)nullptr, d_kernel_mf);
     return check_launch("rec_flen_bwd (fold)");
   }
-  REC_REQUIRE(ids && kernel_mf && FW && dH && g && status && workspace, REC_EINVAL, "null pointer argument");
+  REC_REQUIRE(ids && kernel_mf && FW && dH && g && status, REC_EINVAL, "null pointer argument");
   REC_REQUIRE((const float*)g != FW && (const float*)g != dH, REC_EINVAL, "flen: g must not be FW or dH");
   const int grid = (int)flen_bwd_grid(batch, sb);
   const size_t need = (size_t)grid * (size_t)P * sizeof(float);
   REC_REQUIRE(workspace_bytes >= need, REC_EWORKSPACE, "flen bwd workspace %zu < %zu bytes", workspace_bytes, need);
+  REC_REQUIRE(workspace, REC_EINVAL, "null pointer argument");
   float* part = (float*)workspace;
   const bool vec = flen_vec_ok(g, g_stride);
   rc = dispatch_row_shape(emb_dim, vec ? 4 : 1, [&](auto vec_, auto lanes) -> int {

@@ -278,7 +278,13 @@ extern "C" int rec_gate_emb_bwd(int64_t n, int32_t num_fields, int32_t emb_dim, 
                        num_fields, (const float*)nullptr, d_gate_w);
     return check_launch("rec_gate_emb_bwd (fold)");
   }
-  REC_REQUIRE(ids && W && gate_w && g && d_gate_w && status && workspace, REC_EINVAL, "null pointer argument");
+  REC_REQUIRE(ids && W && gate_w && g && d_gate_w && status, REC_EINVAL, "null pointer argument");
+  {   // the caller is held to the ONE figure of the query (the lane shape with the most blocks), whatever shape runs
+    size_t owed = 0;
+    rec_gate_emb_bwd_workspace_bytes(n, num_fields, &owed);
+    REC_REQUIRE(workspace_bytes >= owed, REC_EWORKSPACE, "gate emb bwd workspace %zu < %zu bytes", workspace_bytes, owed);
+    REC_REQUIRE(workspace, REC_EINVAL, "null pointer argument");
+  }
   const bool vec = gate_vec_ok(W, row_stride) && gate_vec_ok(g, g_stride);
   float* part = (float*)workspace;
   int grid = 0;

@@ -841,13 +841,18 @@ static bool x3_eligible(const rec_gemm_desc* d) {
     return false;
   return x3_cols(d->n).nt > 0 && x3_epilogue_ok(d->epilogue);
 }
-static bool launch_x3(const rec_gemm_desc* d, const float* A, const float* B, float* C, const EpiArgs& e,
-                      const void* b_image, void* workspace, size_t workspace_bytes, hipStream_t st) {
+// shape, alignment and epilogue operands of this call fit the bf16 x 3 forward / dX kernel
+static bool x3_call_ok(const rec_gemm_desc* d, const float* A, const float* C, const EpiArgs& e) {
   if (!x3_eligible(d)) return false;
   if (!x3_shape_ok(d->m, d->n, d->k, d->lda, d->ldc, A, C)) return false;
   if (e.aux0 && (e.ld0 % 4 || ((uintptr_t)e.aux0) % 16)) return false;                 // float4 aux operands
   if (e.aux1 && (e.ld1 % 4 || ((uintptr_t)e.aux1) % 16)) return false;
   if (e.out2 && (e.ld2 % 4 || ((uintptr_t)e.out2) % 16)) return false;
+  return true;
+}
+static bool launch_x3(const rec_gemm_desc* d, const float* A, const float* B, float* C, const EpiArgs& e,
+                      const void* b_image, void* workspace, size_t workspace_bytes, hipStream_t st) {
+  if (!x3_call_ok(d, A, C, e)) return false;
   if (b_image && ((uintptr_t)b_image) % 16 == 0)       // the caller split B ahead of time (rec_gemm_b_images)
     return x3_launch_gemm(d->epilogue, d->m, d->n, d->k, A, d->lda, (const char*)b_image, C, d->ldc, e, st) == REC_OK;
   if (!workspace || ((uintptr_t)workspace) % 16 || workspace_bytes < x3_image_bytes(d->k, d->n)) return false;   // sized without it
@@ -911,8 +916,8 @@ static bool launch_x3_dw(const rec_gemm_desc* d, const float* A, const float* B,
 
 using namespace rec;
 
-// what the exact-f32 kernels need (the bf16 x 3 forms ask for more; a caller that sized its workspace with the switch off
-// gets the exact-f32 kernels when it is flipped on, not an error)
+// what the exact-f32 kernels need (the bf16 x 3 forms ask for more: a call that would take one of them is held to what
+// rec_gemm_f32_workspace_bytes names for it — REC_EWORKSPACE below that, not a silent change of kernel family)
 static size_t plain_workspace_bytes(const rec_gemm_desc* desc) {
   if (skinny_dw(desc)) {
     const size_t z = (size_t)((desc->k + kSkinnyKC - 1) / kSkinnyKC);
@@ -1016,6 +1021,14 @@ extern "C" int rec_gemm_f32_pair(const rec_gemm_desc* desc0, const float* A0, co
                                  size_t workspace_bytes, void* stream) {
   if (int rc = check_gemm(desc0)) return rc;
   if (int rc = check_gemm(desc1)) return rc;
+  {   // the larger of the two queries, checked before EITHER launch: a refused pair has written neither C0 nor C1
+    size_t q0 = 0, q1 = 0;
+    rec_gemm_f32_workspace_bytes(desc0, &q0);
+    rec_gemm_f32_workspace_bytes(desc1, &q1);
+    const size_t owed = q0 > q1 ? q0 : q1;
+    REC_REQUIRE(owed == 0 || (workspace && workspace_bytes >= owed), REC_EWORKSPACE, "workspace %zu < %zu", workspace_bytes,
+                owed);
+  }
   static const rec_gemm_epilogue_args kNoArgs = {};
   const rec_gemm_epilogue_args* y0 = x0 ? x0 : &kNoArgs;
   const rec_gemm_epilogue_args* y1 = x1 ? x1 : &kNoArgs;
@@ -1112,6 +1125,15 @@ extern "C" int rec_gemm_f32(const rec_gemm_desc* desc, const float* A, const flo
                          desc->n, z, (const float*)cpart2, b_colsum);
     set_route(REC_GEMM_ROUTE_SKINNY_DW, -1, z);
     return check_launch("rec_gemm_f32 (skinny dW)");
+  }
+  {   // a call of the bf16 x 3 family owes the bytes its query named (partial tiles; op(B)'s image unless one is handed in)
+    X3DwPlan pl;
+    size_t owed = 0;
+    if ((x3_dw_eligible(desc, &pl) && ((uintptr_t)A) % 16 == 0 && ((uintptr_t)B) % 16 == 0 && ((uintptr_t)C) % 16 == 0) ||
+        (!b_colsum && x3_call_ok(desc, A, C, e) && !(x->b_image && ((uintptr_t)x->b_image) % 16 == 0)))
+      rec_gemm_f32_workspace_bytes(desc, &owed);       // the query's own figure, rounding included
+    REC_REQUIRE(owed == 0 || (workspace && workspace_bytes >= owed), REC_EWORKSPACE, "workspace %zu < %zu", workspace_bytes,
+                owed);
   }
   if (launch_x3_dw(desc, A, B, C, e, b_colsum, workspace, workspace_bytes, st)) return check_launch("rec_gemm_f32 (bf16x3 dW)");
   // tall problems of the towers' own widths: whole row panels, one resident round (gemm_panel.h)

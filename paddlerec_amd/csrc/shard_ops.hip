@@ -116,17 +116,19 @@ extern "C" int rec_shard_route(int64_t n, int32_t num_slots, int64_t num_rows, i
   REC_REQUIRE(send_counts && status, REC_EINVAL, "null pointer argument");
   hipStream_t st = (hipStream_t)stream;
   const int G = num_shards;
+  RoutePlan p;
+  if (n > 0) {     // every check before the first launch: a refused call writes nothing, send_counts included
+    REC_REQUIRE(ids && send_local_row && send_pos && send_sample && slot_of_pos, REC_EINVAL,
+                "null pointer argument");
+    if (int rc = plan_route(n, G, &p)) return rc;
+    REC_REQUIRE(workspace && workspace_bytes >= p.total, REC_EWORKSPACE, "workspace %zu < %zu",
+                workspace_bytes, p.total);
+  }
   if (hipMemsetAsync(send_counts, 0, (size_t)(G + 1) * sizeof(int64_t), st) != hipSuccess) {
     set_error("memset of send_counts failed");
     return REC_EHIP;
   }
   if (n == 0) return REC_OK;
-  REC_REQUIRE(ids && send_local_row && send_pos && send_sample && slot_of_pos, REC_EINVAL,
-              "null pointer argument");
-  RoutePlan p;
-  if (int rc = plan_route(n, G, &p)) return rc;
-  REC_REQUIRE(workspace && workspace_bytes >= p.total, REC_EWORKSPACE, "workspace %zu < %zu",
-              workspace_bytes, p.total);
   char* base = (char*)workspace;
   uint32_t* keys_in = (uint32_t*)(base + p.off_keys_in);
   uint32_t* keys_out = (uint32_t*)(base + p.off_keys_out);

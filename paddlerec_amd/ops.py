@@ -1791,11 +1791,13 @@ def din_attention_pool(hist_item, hist_cat, tgt_item_seq, tgt_cat_seq, mask, w_h
         if nbytes.value:
             wk = ws.get(nbytes.value)
             nb = wk.numel()
-    check(lib().rec_din_attention_pool_fwd_ws(
-        C.byref(d), _p(hist_item), _p(hist_cat), _p(tgt_item_seq), _p(tgt_cat_seq), _p(mask),
-        _p(w_hist_item), _p(w_hist_cat), _p(w_tgt_item_seq), _p(w_tgt_cat_seq), _p(att_w[0]), _p(att_b[0]),
-        _p(att_w[1]), _p(att_b[1]), _p(att_w[2]), _p(att_b[2]), _p(out), _p(attw), _p(act1), _p(status), _p(wk),
-        C.c_size_t(nb), _stream()), "rec_din_attention_pool_fwd_ws")
+    args = (C.byref(d), _p(hist_item), _p(hist_cat), _p(tgt_item_seq), _p(tgt_cat_seq), _p(mask),
+            _p(w_hist_item), _p(w_hist_cat), _p(w_tgt_item_seq), _p(w_tgt_cat_seq), _p(att_w[0]), _p(att_b[0]),
+            _p(att_w[1]), _p(att_b[1]), _p(att_w[2]), _p(att_b[2]), _p(out), _p(attw), _p(act1), _p(status))
+    if ws is None:           # no workspace at all: the entry point without one (the _ws form owes what its query names)
+        check(lib().rec_din_attention_pool_fwd(*args, _stream()), "rec_din_attention_pool_fwd")
+    else:
+        check(lib().rec_din_attention_pool_fwd_ws(*args, _p(wk), C.c_size_t(nb), _stream()), "rec_din_attention_pool_fwd_ws")
     if saved is not None:
         saved["out"], saved["act1"] = out, act1
     return out, attw, status
@@ -1830,11 +1832,13 @@ def din_attention_pool_bwd(hist_item, hist_cat, tgt_item_seq, tgt_cat_seq, w_his
         if nbytes.value:
             wk = ws.get(nbytes.value)
             nb = wk.numel()
-    check(lib().rec_din_attention_pool_bwd_ws(
-        C.byref(d), _p(hist_item), _p(hist_cat), _p(tgt_item_seq), _p(tgt_cat_seq), _p(w_hist_item),
-        _p(w_hist_cat), _p(w_tgt_item_seq), _p(w_tgt_cat_seq), _p(att_w[0]), _p(w1t), _p(att_b[0]),
-        _p(att_w[1]), _p(att_b[1]), _p(att_w[2]), _p(att_weight), _p(out_s), _p(act1_s), _p(d_out), _p(dh), _p(dq),
-        _p(wk), C.c_size_t(nb), _stream()), "rec_din_attention_pool_bwd_ws")
+    args = (C.byref(d), _p(hist_item), _p(hist_cat), _p(tgt_item_seq), _p(tgt_cat_seq), _p(w_hist_item),
+            _p(w_hist_cat), _p(w_tgt_item_seq), _p(w_tgt_cat_seq), _p(att_w[0]), _p(w1t), _p(att_b[0]),
+            _p(att_w[1]), _p(att_b[1]), _p(att_w[2]), _p(att_weight), _p(out_s), _p(act1_s), _p(d_out), _p(dh), _p(dq))
+    if ws is None:
+        check(lib().rec_din_attention_pool_bwd(*args, _stream()), "rec_din_attention_pool_bwd")
+    else:
+        check(lib().rec_din_attention_pool_bwd_ws(*args, _p(wk), C.c_size_t(nb), _stream()), "rec_din_attention_pool_bwd_ws")
     return dh, dq
 
 

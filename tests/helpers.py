@@ -270,3 +270,71 @@ def assert_adam_weights_close(got, want, lr, steps, rel=1e-5, frac=0.98, err_msg
     assert float(err.max()) <= cap, "%s max err %.3e exceeds what %d Adam steps of lr %.3g can move (%.3e)" % (
         err_msg, float(err.max()), steps, lr, cap)
     return tight
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# The C-ABI's buffer contract (include/recengine.h: "the caller owns every buffer", sized by the *_bytes queries).
+class GuardedWorkspace:
+    """Duck-typed stand-in for paddlerec_amd.ops.Workspace that hands out EXACTLY the bytes a wrapper asks for, inside
+    one allocation  [ front guard | nbytes | rear guard ]  with guard = max(64 KiB, nbytes) rounded up to 256.  The
+    whole allocation is filled with `fill` before each get() (refill=False keeps what the previous call left: the
+    stale-reuse check), so a kernel that reads scratch it did not write sees 0xFF (NaN as a float, all-ones as a ticket
+    or histogram word) or 0x00, and one that writes past its declared bytes lands in a guard — a failed intact(), not a
+    fault.  The view is 256-byte aligned.
+
+    short=k: the view is nbytes - k bytes (what a refusal test passes); the rear guard still starts where the full view
+    would end, so a call that ignores the size stays inside the allocation.
+    nbytes == 0 (asked for, or left by short): zero_view=False returns a zero-length view (torch reports a null
+    data_ptr() for it); zero_view=True returns a 256-byte view for entry points that want a non-null workspace even when
+    the query says 0.
+
+    gets: every (nbytes asked for, view handed out)."""
+    MIN_GUARD = 64 * 1024
+    ALIGN = 256
+
+    def __init__(self, device, fill=0xFF, short=0, refill=True, zero_view=False):
+        self.device, self.fill, self.short, self.refill, self.zero_view = device, int(fill), int(short), refill, zero_view
+        self.gets = []
+        self.buf = None
+        self._lo = self._hi = 0       # the handed-out bytes are buf[_lo:_hi]
+        self._gmax = 0
+
+    @classmethod
+    def guard_bytes(cls, nbytes):
+        g = max(cls.MIN_GUARD, int(nbytes))
+        return (g + cls.ALIGN - 1) // cls.ALIGN * cls.ALIGN
+
+    def get(self, nbytes):
+        import torch
+        nbytes = int(nbytes)
+        guard = self.guard_bytes(nbytes)
+        if not self.refill:            # stale reuse: every view starts at one offset, so a call sees its predecessor's bytes
+            guard = self._gmax = max(self._gmax, guard)
+        total = guard + nbytes + guard + self.ALIGN          # + ALIGN: room to align the view whatever the allocator gave
+        stale = None
+        if self.buf is None or self.buf.numel() < total:
+            if self.buf is not None and not self.refill:
+                stale = self.buf[self._lo:]                  # grow-only, as ops.Workspace: what the last view held stays
+            self.buf = torch.full((total,), self.fill, dtype=torch.uint8, device=self.device)
+        elif self.refill:
+            self.buf.fill_(self.fill)
+        base = (-self.buf.data_ptr()) % self.ALIGN
+        lo = base + guard
+        if stale is not None:
+            stale = stale[:self.buf.numel() - lo]
+            self.buf[lo:lo + stale.numel()] = stale          # ... at the start of the next one
+        want = max(nbytes - self.short, 0)
+        if want == 0 and self.zero_view:
+            want = self.ALIGN
+        self._lo, self._hi = lo, lo + want
+        view = self.buf[lo:lo + want]
+        self.gets.append((nbytes, view))
+        return view
+
+    def intact(self):
+        """Both guards (every byte of the allocation outside the last view) still hold the fill byte.  Only meaningful
+        with refill=True, or before anything stale was kept."""
+        if self.buf is None:
+            return True
+        f = self.fill
+        return bool((self.buf[:self._lo] == f).all().item()) and bool((self.buf[self._hi:] == f).all().item())
