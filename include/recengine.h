@@ -248,6 +248,21 @@ int rec_ids_group_payload(int64_t n, int32_t num_slots, int64_t num_rows, int64_
                           const int64_t* ids, const int64_t* slot_offset, const int32_t* payload,
                           int32_t* sorted_pos, int64_t* uniq_rows, int32_t* seg_offset, int32_t* n_uniq,
                           int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+/* Host query (touches no device): the radix-sort plan rec_ids_group / rec_ids_group_payload — and the general path of
+ * rec_ids_group_slots, with n = batch * num_slots and num_rows = num_slots * slot_rows — run for n lookups of a
+ * num_rows-row table in this process.  The plan depends on sizes (key width of num_rows, 4 Mi / 8 Mi lookup thresholds)
+ * and on the process environment (REC_RSORT_DIGIT, REC_RSORT_PACK, REC_GROUP_DROP, read once); the entry points execute
+ * exactly what this reports, so a test that means one path asserts it here instead of trusting its shape.  n == 0:
+ * nothing is sorted, passes = 0. */
+typedef struct {
+  int32_t passes;    /* LSD passes over the key (keys take the values 0 .. num_rows; num_rows = the dropped lookups) */
+  int32_t bits[8];   /* digit width of pass i, least significant digit first; 0 behind the last pass */
+  int32_t waves;     /* waves per block: 4 (tiles of 2048 lookups) or 16 (tiles of 8192) */
+  int32_t key_bytes; /* 4: uint32_t keys (num_rows < 0xFFFFFFFF), 8: uint64_t keys */
+  int32_t packed;    /* 1: the intermediate passes move packed (key, value) pairs and alias the key buffers */
+  int32_t drop;      /* 1: padding / out-of-range lookups leave the sort after its first pass */
+} rec_ids_group_plan_t;
+int rec_ids_group_plan(int64_t n, int64_t num_rows, rec_ids_group_plan_t* out);
 
 /* The same grouping for a [batch, num_slots] id batch whose slot s owns rows [s * slot_rows, (s + 1) * slot_rows) of the
  * table (BASELINE configs[1]: 26 tables x 1 000 000 rows as one table; deepfm/net.py:62-86 with one nn.Embedding per

@@ -189,6 +189,12 @@ class GemmRoute(C.Structure):
     _fields_ = [("family", C.c_int32), ("cfg", C.c_int32), ("splits", C.c_int32), ("flags", C.c_int32)]
 
 
+class IdsGroupPlan(C.Structure):
+    """rec_ids_group_plan_t (include/recengine.h)."""
+    _fields_ = [("passes", C.c_int32), ("bits", C.c_int32 * 8), ("waves", C.c_int32), ("key_bytes", C.c_int32),
+                ("packed", C.c_int32), ("drop", C.c_int32)]
+
+
 GEMM_ROUTE_FAMILIES = ("skinny_rows", "skinny_dw", "x3_dw", "x3", "panel", "glds", "direct", "tiled")
 GEMM_ROUTE_FLAGS = dict(fast=1, pipe=2, vec=4, ks4=8, fold=16, vec_a=32, pair=64)
 GEMM_CFGS = ("128x80", "256x80", "256x128", "128x128", "80x80", "64x80", "128x80_o4", "144x80")
@@ -303,6 +309,7 @@ SIGNATURES = {
     "rec_emb_sumpool_bwd": (C.c_int, [_I64, _I32, _P, _P, _P, _P]),
     "rec_ids_group_workspace_bytes": (C.c_int, [_I64, _I64, C.POINTER(_SZ)]),
     "rec_ids_group": (C.c_int, [_I64, _I32, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "rec_ids_group_plan": (C.c_int, [_I64, _I64, C.POINTER(IdsGroupPlan)]),
     "rec_ids_group_payload": (C.c_int, [_I64, _I32, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "rec_ids_group_slots_workspace_bytes": (C.c_int, [_I64, _I32, _I64, C.POINTER(_SZ)]),
     "rec_ids_group_slots": (C.c_int, [_I64, _I32, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),

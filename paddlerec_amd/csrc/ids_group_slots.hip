@@ -10,8 +10,8 @@
 // of B keys below 2^20.  Here:
 //   keys    : [B,S] i64 -> [S][B] u32 slot-local keys (LDS transpose; padding / out-of-range -> no key, rank = -1)
 //   hist    : block (slot, chunk of 8192) -> digit histogram [slot][chunk][bin]
-//   scatter : the block scans its slot's [chunks][bins] matrix itself (8 x 1024 counters from L2: no rowscan launch,
-//             no global bin totals), ranks its 8192 keys with ballots (stable) and scatters inside the slot's 256 KB
+//   scatter : the block scans its slot's [chunks][bins] matrix itself (<= kMaxChunks = 32 chunks x <= 1024 bins from
+//             L2, 8 x 1024 at batch 65536: no rowscan launch, no global bin totals), ranks its 8192 keys with ballots (stable) and scatters inside the slot's 256 KB
 //             (L2-resident); two digits of <= 10 bits; the final pass writes sorted_pos, the global rows and — new —
 //             rank[pos] = sorted index, the inverse permutation (fm_bwd writes its row gradients in SORTED order through
 //             it, so the row-update kernel streams them: rec_grad_layout.sorted)

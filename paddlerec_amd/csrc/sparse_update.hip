@@ -183,61 +183,67 @@ static int key_bits(int64_t N) {
   return b;
 }
 
-template <class KeyT>
+static bool use_u32_keys(int64_t N) { return N < 0xFFFFFFFFll; }   // keys 0..N (N = sentinel) fit a uint32_t
+
+// Everything the grouping sort decides from (n, N) and the process environment, in ONE place: run_group executes this
+// plan, rec_ids_group_workspace_bytes sizes it and rec_ids_group_plan reports it — a test asserts the path it means to
+// cover instead of trusting its shape.
 struct GroupPlan {
   rsort::Plan sort;
+  bool u32;      // 32-bit keys (else 64-bit)
+  bool packed;   // rsort::sort_pairs_packed: the intermediate passes ping-pong packed (key, value) pairs
+  bool drop;     // padding and out-of-range lookups leave the sort after its first pass
   size_t off_keys_tmp, off_keys_dst, off_vals_tmp, off_hist, off_totals, off_nlive, off_cnt, total;
 };
 
-template <class KeyT>
-static int plan_group(int64_t n, int64_t N, GroupPlan<KeyT>* p) {
-  p->sort = rsort::make_plan(n, key_bits(N));
+static GroupPlan plan_group(int64_t n, int64_t N) {
+  GroupPlan p;
+  p.u32 = use_u32_keys(N);
+  p.sort = rsort::make_plan(n, key_bits(N));
+  // padding and out-of-range lookups leave the sort after its first pass (REC_GROUP_DROP=0: carried through every pass)
+  static const bool drop = [] { const char* v = getenv("REC_GROUP_DROP"); return !(v && *v == '0'); }();
+  p.drop = drop && n < (1ll << 31);
+  // packed intermediate passes: measured on the gpubox model's 40 M lookups (sort alone 1.425 -> 1.361 ms, step -0.1 ms)
+  // and on the 1.7 M lookups of a DeepFM batch on one shared table (step +8 us): taken from 4 M lookups on
+  // (REC_RSORT_PACK=0 / 1: never / always)
+  static const int pack = [] { const char* v = getenv("REC_RSORT_PACK"); return v && *v ? atoi(v) : -1; }();
+  p.packed = p.u32 && p.sort.passes >= 2 && (pack == 1 || (pack < 0 && n >= (4ll << 20)));
+  const size_t key_size = p.u32 ? sizeof(uint32_t) : sizeof(uint64_t);
   size_t o = 0;
-  p->off_keys_tmp = o; o += align_up((size_t)n * sizeof(KeyT), 256);
-  p->off_keys_dst = o; o += align_up((size_t)n * sizeof(KeyT), 256);
+  p.off_keys_tmp = o; o += align_up((size_t)n * key_size, 256);
+  p.off_keys_dst = o; o += align_up((size_t)n * key_size, 256);
   // (32-bit keys, >= 2 passes: the intermediate passes ping-pong PACKED pairs — pairs_a = the keys_tmp | keys_dst region,
   // pairs_b = this region, n uint2 — see rsort::sort_pairs_packed)
-  p->off_vals_tmp = o; o += align_up((size_t)n * (sizeof(KeyT) == 4 ? 8 : sizeof(int32_t)), 256);
-  p->off_hist = o;     o += p->sort.hist_bytes;
-  p->off_totals = o;   o += p->sort.totals_bytes;
-  p->off_nlive = o;    o += 256;
-  p->off_cnt = o;      o += align_up((size_t)((n + kHeadsTile - 1) / kHeadsTile + 1) * 2 * sizeof(int32_t), 256);
-  p->total = o;
-  return REC_OK;
+  p.off_vals_tmp = o; o += align_up((size_t)n * (p.u32 ? 8 : sizeof(int32_t)), 256);
+  p.off_hist = o;     o += p.sort.hist_bytes;
+  p.off_totals = o;   o += p.sort.totals_bytes;
+  p.off_nlive = o;    o += 256;
+  p.off_cnt = o;      o += align_up((size_t)((n + kHeadsTile - 1) / kHeadsTile + 1) * 2 * sizeof(int32_t), 256);
+  p.total = o;
+  return p;
 }
 
 template <class KeyT>
-static int run_group(int64_t n, int S, int64_t N, int64_t pad, const int64_t* ids,
+static int run_group(const GroupPlan& p, int64_t n, int S, int64_t N, int64_t pad, const int64_t* ids,
                      const int64_t* slot_off, const int32_t* payload, int32_t* sorted_pos, int64_t* uniq,
                      int32_t* seg_off, int32_t* n_uniq, int32_t* status, void* ws, size_t ws_bytes,
-                     hipStream_t st, int64_t slot_rows = 0) {
-  GroupPlan<KeyT> p;
-  if (int rc = plan_group<KeyT>(n, N, &p)) return rc;
+                     hipStream_t st, int64_t slot_rows) {
   REC_REQUIRE(ws && ws_bytes >= p.total, REC_EWORKSPACE, "workspace %zu < %zu", ws_bytes, p.total);
   char* base = (char*)ws;
   KeyT* keys_tmp = (KeyT*)(base + p.off_keys_tmp);
   KeyT* keys_dst = (KeyT*)(base + p.off_keys_dst);
   int32_t* vals_tmp = (int32_t*)(base + p.off_vals_tmp);
   int32_t* cnt = (int32_t*)(base + p.off_cnt);
-  // padding and out-of-range lookups leave the sort after its first pass (REC_GROUP_DROP=0: carried through every pass)
-  static const bool drop = [] { const char* v = getenv("REC_GROUP_DROP"); return !(v && *v == '0'); }();
-  const bool dr = drop && n < (1ll << 31);
+  const bool dr = p.drop;
   IdsSrc<KeyT> src{ids, slot_off, S, N, pad, status, payload, dr, slot_rows};
-  // packed intermediate passes: measured on the gpubox model's 40 M lookups (sort alone 1.425 -> 1.361 ms, step -0.1 ms)
-  // and on the 1.7 M lookups of a DeepFM batch on one shared table (step +8 us): taken from 4 M lookups on
-  // (REC_RSORT_PACK=0 / 1: never / always)
-  static const int pack = [] { const char* v = getenv("REC_RSORT_PACK"); return v && *v ? atoi(v) : -1; }();
-  bool packed = false;
   if constexpr (sizeof(KeyT) == 4) {
-    if (p.sort.passes >= 2 && (pack == 1 || (pack < 0 && n >= (4ll << 20)))) {
-      packed = true;
+    if (p.packed)
       if (int rc = rsort::sort_pairs_packed(n, p.sort, src, (uint2*)keys_tmp, (uint2*)vals_tmp, (uint32_t*)keys_dst,
                                             sorted_pos, base + p.off_hist, base + p.off_totals, st,
                                             dr ? (int32_t*)(base + p.off_nlive) : nullptr, (uint32_t)N))
         return rc;
-    }
   }
-  if (!packed)
+  if (!p.packed)
     if (int rc = rsort::sort_pairs<KeyT>(n, p.sort, src, keys_tmp, vals_tmp, keys_dst, sorted_pos,
                                          base + p.off_hist, base + p.off_totals, st,
                                          dr ? (int32_t*)(base + p.off_nlive) : nullptr, (KeyT)N))
@@ -250,6 +256,18 @@ static int run_group(int64_t n, int S, int64_t N, int64_t pad, const int64_t* id
   hipLaunchKernelGGL(heads_emit_kernel<KeyT>, dim3(nblk), dim3(rsort::kThreads), 0, st, n, (KeyT)N, keys_dst, cnt,
                      uniq, seg_off);
   return check_launch("rec_ids_group");
+}
+
+// plan once, then the kernels of the key width the plan names
+static int run_group_any(int64_t n, int S, int64_t N, int64_t pad, const int64_t* ids, const int64_t* slot_off,
+                         const int32_t* payload, int32_t* sorted_pos, int64_t* uniq, int32_t* seg_off, int32_t* n_uniq,
+                         int32_t* status, void* ws, size_t ws_bytes, hipStream_t st, int64_t slot_rows = 0) {
+  const GroupPlan p = plan_group(n, N);
+  if (p.u32)
+    return run_group<uint32_t>(p, n, S, N, pad, ids, slot_off, payload, sorted_pos, uniq, seg_off, n_uniq, status, ws,
+                               ws_bytes, st, slot_rows);
+  return run_group<uint64_t>(p, n, S, N, pad, ids, slot_off, payload, sorted_pos, uniq, seg_off, n_uniq, status, ws,
+                             ws_bytes, st, slot_rows);
 }
 
 // ---------------------------------------------------------------- long-segment partial sums
@@ -1614,21 +1632,26 @@ static void adam_scalars(const rec_adam_hyper* h, float* lr_t, float* eps_t) {
 
 using namespace rec;
 
-static bool use_u32_keys(int64_t N) { return N < 0xFFFFFFFFll; }
-
 extern "C" int rec_ids_group_workspace_bytes(int64_t n, int64_t num_rows, size_t* bytes) {
   REC_REQUIRE(bytes && n >= 0 && num_rows > 0, REC_EINVAL, "bad arguments");
   REC_REQUIRE(n < (1ll << 31) - 1, REC_ESHAPE, "n too large for int32 positions");
   if (n == 0) { *bytes = 256; return REC_OK; }
-  if (use_u32_keys(num_rows)) {
-    GroupPlan<uint32_t> p;
-    if (int rc = plan_group<uint32_t>(n, num_rows, &p)) return rc;
-    *bytes = p.total;
-  } else {
-    GroupPlan<uint64_t> p;
-    if (int rc = plan_group<uint64_t>(n, num_rows, &p)) return rc;
-    *bytes = p.total;
-  }
+  *bytes = plan_group(n, num_rows).total;
+  return REC_OK;
+}
+
+extern "C" int rec_ids_group_plan(int64_t n, int64_t num_rows, rec_ids_group_plan_t* out) {
+  REC_REQUIRE(out && n >= 0 && num_rows > 0, REC_EINVAL, "bad arguments");
+  REC_REQUIRE(n < (1ll << 31) - 1, REC_ESHAPE, "n too large for int32 positions");
+  memset(out, 0, sizeof(*out));
+  out->key_bytes = use_u32_keys(num_rows) ? 4 : 8;
+  if (n == 0) return REC_OK;       // nothing is sorted: passes = 0
+  const GroupPlan p = plan_group(n, num_rows);
+  out->passes = p.sort.passes;
+  for (int i = 0; i < p.sort.passes; ++i) out->bits[i] = p.sort.bits[i];
+  out->waves = p.sort.waves;
+  out->packed = p.packed ? 1 : 0;
+  out->drop = p.drop ? 1 : 0;
   return REC_OK;
 }
 
@@ -1648,12 +1671,8 @@ extern "C" int rec_ids_group_payload(int64_t n, int32_t num_slots, int64_t num_r
     return REC_OK;
   }
   REC_REQUIRE(ids, REC_EINVAL, "ids is NULL");
-  if (use_u32_keys(num_rows))
-    return run_group<uint32_t>(n, num_slots, num_rows, padding_idx, ids, slot_offset, payload, sorted_pos,
-                               uniq_rows, seg_offset, n_uniq, status, workspace, workspace_bytes,
-                               st);
-  return run_group<uint64_t>(n, num_slots, num_rows, padding_idx, ids, slot_offset, payload, sorted_pos,
-                             uniq_rows, seg_offset, n_uniq, status, workspace, workspace_bytes, st);
+  return run_group_any(n, num_slots, num_rows, padding_idx, ids, slot_offset, payload, sorted_pos, uniq_rows,
+                       seg_offset, n_uniq, status, workspace, workspace_bytes, st);
 }
 
 extern "C" int rec_ids_group(int64_t n, int32_t num_slots, int64_t num_rows, int64_t padding_idx,
@@ -1716,13 +1735,8 @@ extern "C" int rec_ids_group_slots(int64_t batch, int32_t num_slots, int64_t slo
     return sg::run(batch, num_slots, slot_rows, padding_idx, ids, sorted_pos, uniq_rows, seg_offset, n_uniq, rank, status,
                    workspace, workspace_bytes, st);
   const int64_t N = slot_rows * num_slots;
-  int rc;
-  if (use_u32_keys(N))
-    rc = run_group<uint32_t>(n, num_slots, N, padding_idx, ids, nullptr, nullptr, sorted_pos, uniq_rows, seg_offset,
-                             n_uniq, status, workspace, workspace_bytes, st, slot_rows);
-  else
-    rc = run_group<uint64_t>(n, num_slots, N, padding_idx, ids, nullptr, nullptr, sorted_pos, uniq_rows, seg_offset,
-                             n_uniq, status, workspace, workspace_bytes, st, slot_rows);
+  const int rc = run_group_any(n, num_slots, N, padding_idx, ids, nullptr, nullptr, sorted_pos, uniq_rows, seg_offset,
+                               n_uniq, status, workspace, workspace_bytes, st, slot_rows);
   if (rc != REC_OK || !rank) return rc;
   return rec_ids_rank(n, n_uniq, sorted_pos, rank, stream);
 }
