@@ -1863,6 +1863,55 @@ int rec_bst_embed_bwd(int64_t batch, int32_t steps, const int32_t* widths, const
 int rec_bst_possum_fwd(int64_t batch, int32_t positions, const float* z, const float* bias, float* y, void* stream);
 int rec_bst_possum_bwd(int64_t batch, int32_t positions, const float* dy, float* dz, float* dbias, void* stream);
 
+/* ----------------------------------------------------------------------------------------
+ * The multitask family (models/multitask/mmoe, ple): the gate softmax, the gate-weighted mixture of expert outputs and the
+ * two-class softmax / clip / log-loss head (csrc/mtl_ops.hip).  float32, no atomics, no workspace; every output element
+ * is produced by one thread or one fixed-order fold, so a rerun is bit-identical.  Arguments are checked on the host
+ * before any launch (REC_EINVAL); batch == 0 returns REC_OK without a launch.
+ *
+ * rec_mtl_mix_desc: H is [batch, n_slots * expert_size], n_slots column blocks of expert_size floats (the experts'
+ *   post-ReLU outputs, a column range of the packed expert | gate GEMM's output).  Gate g mixes the expert slots
+ *   [first0[g], first0[g] + count0[g]) followed by [first1[g], first1[g] + count1[g]), in that order: count0 >= 1,
+ *   count1 >= 0, count0 + count1 <= 64, the two ranges disjoint and inside n_slots (first1 is not read when count1 is 0).
+ *   MMoE uses one range per gate, PLE's task gates two (own experts, then the shared ones).  With n_g = count0[g] +
+ *   count1[g], gate g's logits, probabilities and logit gradients occupy columns [sum_{g' < g} n_g', + n_g).
+ *   Limits: expert_size 1..1024, n_slots 1..128, n_gates 1..16.  Row strides in floats; 0 means packed (n_slots *
+ *   expert_size for ld_h / ld_dh, sum n_g for ld_logit / ld_prob / ld_dlogit, n_gates * expert_size for ld_out, which
+ *   mix and dmix share); a non-zero value below the packed width is refused.  Columns beyond the packed width of a strided
+ *   output are not touched.  float4 accesses are used when expert_size, ld_h, ld_out (and ld_dh) are multiples of 4 and
+ *   H, mix / dmix (and dH) are 16-byte aligned; anything else runs the scalar form.
+ * rec_mtl_mix_fwd: prob_g = softmax(logits_g) per row (maximum subtracted);
+ *   mix[b, g * S + s] = sum_j prob[b, g, j] * H[b, slot(g, j) * S + s], j ascending.  prob is kept for the backward.
+ * rec_mtl_mix_bwd: dp[g, j] = sum_s dmix[b, g, s] H[b, slot(g, j), s];  dlogits[g, j] = prob[g, j] (dp[g, j] - sum_k
+ *   prob[g, k] dp[g, k]);  dH[b, e, s] = sum over the gates that select slot e, g ascending, of prob dmix[b, g, s],
+ *   multiplied by (H > 0) when relu != 0 (the experts' ReLU).  A slot no gate selects gets zeros.  No output aliases an
+ *   input.
+ * rec_mtl_head: logits [batch, 2 * n_tasks] (row stride ld), label [batch, n_tasks] float (row stride ld_label), n_tasks
+ *   1..REC_MTL_MAX_TASKS; 0 strides mean packed.  Per row and task: p = softmax(logits[2t : 2t + 2]);  pred[b, 2t : 2t + 2] = clip(p,
+ *   1e-15, 1 - 1e-15) evaluated in float32 (the upper bound is 1);  cost[b, t] = -y log(pred1 + 1e-4) - (1 - y) log(1 -
+ *   pred1 + 1e-4) with pred1 the clipped column 1;  dlogits [batch, 2 * n_tasks] (NULL at inference) = the gradient of
+ *   grad_scale * cost through the clip (passing where lo <= p <= hi) and the softmax.  pred, cost and dlogits are packed.
+ * ---------------------------------------------------------------------------------------- */
+#define REC_MTL_MAX_GATES 16
+#define REC_MTL_MAX_SLOTS 128
+#define REC_MTL_MAX_PER_GATE 64
+#define REC_MTL_MAX_EXPERT_SIZE 1024
+#define REC_MTL_MAX_TASKS 16 /* rec_mtl_head's n_tasks */
+typedef struct {
+  int64_t batch;
+  int32_t expert_size;
+  int32_t n_slots;
+  int32_t n_gates;
+  int64_t ld_h, ld_logit, ld_prob, ld_out, ld_dh, ld_dlogit;
+  int32_t first0[REC_MTL_MAX_GATES], count0[REC_MTL_MAX_GATES], first1[REC_MTL_MAX_GATES], count1[REC_MTL_MAX_GATES];
+} rec_mtl_mix_desc;
+
+int rec_mtl_mix_fwd(const rec_mtl_mix_desc* desc, const float* H, const float* logits, float* prob, float* mix, void* stream);
+int rec_mtl_mix_bwd(const rec_mtl_mix_desc* desc, const float* H, const float* prob, const float* dmix, int32_t relu, float* dH,
+                    float* dlogits, void* stream);
+int rec_mtl_head(int64_t batch, int32_t n_tasks, const float* logits, int64_t ld, const float* label, int64_t ld_label,
+                 float grad_scale, float* pred, float* cost, float* dlogits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

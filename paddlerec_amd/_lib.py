@@ -189,6 +189,17 @@ class GemmRoute(C.Structure):
     _fields_ = [("family", C.c_int32), ("cfg", C.c_int32), ("splits", C.c_int32), ("flags", C.c_int32)]
 
 
+REC_MTL_MAX_GATES, REC_MTL_MAX_SLOTS, REC_MTL_MAX_PER_GATE, REC_MTL_MAX_EXPERT_SIZE, REC_MTL_MAX_TASKS = 16, 128, 64, 1024, 16
+
+
+class MtlMixDesc(C.Structure):
+    """rec_mtl_mix_desc (include/recengine.h)."""
+    _fields_ = [("batch", C.c_int64), ("expert_size", C.c_int32), ("n_slots", C.c_int32), ("n_gates", C.c_int32),
+                ("ld_h", C.c_int64), ("ld_logit", C.c_int64), ("ld_prob", C.c_int64), ("ld_out", C.c_int64),
+                ("ld_dh", C.c_int64), ("ld_dlogit", C.c_int64), ("first0", C.c_int32 * 16), ("count0", C.c_int32 * 16),
+                ("first1", C.c_int32 * 16), ("count1", C.c_int32 * 16)]
+
+
 class IdsGroupPlan(C.Structure):
     """rec_ids_group_plan_t (include/recengine.h)."""
     _fields_ = [("passes", C.c_int32), ("bits", C.c_int32 * 8), ("waves", C.c_int32), ("key_bytes", C.c_int32),
@@ -300,6 +311,9 @@ SIGNATURES = {
     "rec_bst_embed_bwd": (C.c_int, [_I64, _I32, C.POINTER(_I32), _P, _I64, C.POINTER(_P), _P]),
     "rec_bst_possum_fwd": (C.c_int, [_I64, _I32, _P, _P, _P, _P]),
     "rec_bst_possum_bwd": (C.c_int, [_I64, _I32, _P, _P, _P, _P]),
+    "rec_mtl_mix_fwd": (C.c_int, [C.POINTER(MtlMixDesc), _P, _P, _P, _P, _P]),
+    "rec_mtl_mix_bwd": (C.c_int, [C.POINTER(MtlMixDesc), _P, _P, _P, _I32, _P, _P, _P]),
+    "rec_mtl_head": (C.c_int, [_I64, _I32, _P, _I64, _P, _I64, _F, _P, _P, _P, _P]),
     "rec_dense_fold_fwd": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P]),
     "rec_dense_fold_bwd": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _I32, _P]),
     "rec_dense_fold_fwd_full": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P]),

@@ -12,7 +12,7 @@ import torch
 
 from . import _lib
 from ._lib import (EPI, AdagradHyper, AdamHyper, CinView, DcnCrossDesc, DeepFMDesc, DinDesc, FatFFMDesc, FEFMDesc, FFMDesc, GemmBImage, GemmDesc, GemmEpilogueArgs, GradLayout,
-                   GradSrc, LazyInit, MultislotDesc, PsAccessor, PsLayout, RecError, check)
+                   GradSrc, LazyInit, MtlMixDesc, MultislotDesc, PsAccessor, PsLayout, RecError, check)
 
 _recorder = None        # paddlerec_amd.plan.CallPlan while a step is being recorded
 
@@ -2464,6 +2464,80 @@ def bst_possum_bwd(dy, P, dbias):
     dz = torch.empty(B * P, 1, dtype=torch.float32, device=dy.device)
     check(lib().rec_bst_possum_bwd(B, int(P), _p(dy), _p(dz), _p(dbias), _stream()), "rec_bst_possum_bwd")
     return dz
+
+
+# ------------------------------------------------------------------ multitask (mmoe, ple): expert-gate mixture, two-class head
+class MtlMix:
+    """The slot map of rec_mtl_mix_fwd / rec_mtl_mix_bwd (rec_mtl_mix_desc): expert_size S, n_slots column blocks of S
+    floats in H, and per gate (first0, count0, first1, count1) — the gate mixes the slots [first0, first0 + count0) then
+    [first1, first1 + count1).  n_logit: the columns of the logits / probabilities (the gates' expert counts, summed)."""
+
+    def __init__(self, expert_size, n_slots, gates):
+        self.expert_size, self.n_slots = int(expert_size), int(n_slots)
+        self.gates = [tuple(int(x) for x in (tuple(g) + (0, 0))[:4]) for g in gates]
+        self.n_gates = len(self.gates)
+        self.n_logit = sum(g[1] + g[3] for g in self.gates)
+
+    def desc(self, batch, ld_h=0, ld_logit=0, ld_prob=0, ld_out=0, ld_dh=0, ld_dlogit=0):
+        d = MtlMixDesc(int(batch), self.expert_size, self.n_slots, self.n_gates, ld_h, ld_logit, ld_prob, ld_out, ld_dh,
+                       ld_dlogit)
+        for i, g in enumerate(self.gates[:_lib.REC_MTL_MAX_GATES]):
+            d.first0[i], d.count0[i], d.first1[i], d.count1[i] = g
+        return d
+
+
+def _mtl_view(t, B, cols, name):
+    """[B, cols] float32 device view with unit column stride -> its row stride (0 = packed where one row hides it)."""
+    ld = _rows_view(t, name)
+    if tuple(t.shape) != (B, cols):
+        raise RecError("%s has shape %s, expected %s" % (name, tuple(t.shape), (B, cols)))
+    return ld if B > 1 else 0
+
+
+def mtl_mix_fwd(mix, H, logits, prob=None, out=None):
+    """Gate softmax + gate-weighted sum of expert outputs (rec_mtl_mix_fwd).  H [B, n_slots*S] and logits [B, n_logit] are
+    2-D views with a row stride (column ranges of the packed GEMM's output); prob [B, n_logit] and out [B, n_gates*S] are
+    allocated when None.  -> (prob, out)."""
+    B = H.shape[0]
+    f32 = dict(dtype=torch.float32, device=H.device)
+    if prob is None:
+        prob = torch.empty(B, mix.n_logit, **f32)
+    if out is None:
+        out = torch.empty(B, mix.n_gates * mix.expert_size, **f32)
+    d = mix.desc(B, _mtl_view(H, B, mix.n_slots * mix.expert_size, "H"), _mtl_view(logits, B, mix.n_logit, "logits"),
+                 _mtl_view(prob, B, mix.n_logit, "prob"), _mtl_view(out, B, mix.n_gates * mix.expert_size, "out"))
+    check(lib().rec_mtl_mix_fwd(C.byref(d), _p(H), _p(logits), _p(prob), _p(out), _stream()), "rec_mtl_mix_fwd")
+    return prob, out
+
+
+def mtl_mix_bwd(mix, H, prob, dmix, relu=True, dH=None, dlogits=None):
+    """Backward of mtl_mix_fwd (rec_mtl_mix_bwd): dH [B, n_slots*S] (masked by H > 0 when relu) and dlogits [B, n_logit],
+    views with a row stride — the two column ranges of the packed image's output gradient.  -> (dH, dlogits)."""
+    B = H.shape[0]
+    f32 = dict(dtype=torch.float32, device=H.device)
+    if dH is None:
+        dH = torch.empty(B, mix.n_slots * mix.expert_size, **f32)
+    if dlogits is None:
+        dlogits = torch.empty(B, mix.n_logit, **f32)
+    d = mix.desc(B, _mtl_view(H, B, mix.n_slots * mix.expert_size, "H"), 0, _mtl_view(prob, B, mix.n_logit, "prob"),
+                 _mtl_view(dmix, B, mix.n_gates * mix.expert_size, "dmix"),
+                 _mtl_view(dH, B, mix.n_slots * mix.expert_size, "dH"), _mtl_view(dlogits, B, mix.n_logit, "dlogits"))
+    check(lib().rec_mtl_mix_bwd(C.byref(d), _p(H), _p(prob), _p(dmix), int(bool(relu)), _p(dH), _p(dlogits), _stream()),
+          "rec_mtl_mix_bwd")
+    return dH, dlogits
+
+
+def mtl_head(logits, label, grad_scale=1.0, want_grad=True):
+    """The head of the multitask nets (rec_mtl_head): logits [B, 2T] and label [B, T] float32 views with a row stride.
+    -> (pred [B, 2T] clipped softmax, cost [B, T] log loss of column 1, dlogits [B, 2T] = d(grad_scale * cost) or None)."""
+    B, T = label.shape
+    f32 = dict(dtype=torch.float32, device=logits.device)
+    ld, ldl = _mtl_view(logits, B, 2 * T, "logits"), _mtl_view(label, B, T, "label")
+    pred, cost = torch.empty(B, 2 * T, **f32), torch.empty(B, T, **f32)
+    dl = torch.empty(B, 2 * T, **f32) if want_grad else None
+    check(lib().rec_mtl_head(B, T, _p(logits), ld, _p(label), ldl, float(grad_scale), _p(pred), _p(cost), _p(dl), _stream()),
+          "rec_mtl_head")
+    return pred, cost, dl
 
 
 # ------------------------------------------------------------------ xDeepFM CIN (the passes around the GEMM)

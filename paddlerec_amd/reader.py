@@ -591,3 +591,44 @@ class AmazonBSTReader:
                 arrs = [np.stack([r[i] for r in group]) for i in range(len(self.SLOTS))]
                 group = []
                 yield tuple(torch.from_numpy(a).to(self.device, non_blocking=True) for a in arrs)
+
+
+class CensusReader:
+    """models/multitask/{mmoe,ple}/census_reader.py RecDataset with the batching of the other readers (drop_last over the
+    concatenation of the files): comma-separated lines of 2 + feature_size numbers — label_marital, label_income, then the
+    features, each float32(float(token)).  Yields (features [B, F] f32, label_income [B, 1] f32, label_marital [B, 1] f32)
+    on `device`, the order of dygraph_model.py's create_feeds.  A label other than 0 or 1 is a ValueError naming file and
+    line: the reference yields an empty label array there and fails later, in the collate (and truncates a fractional
+    label with int(), 0.5 -> 0: also refused here).  The feature
+    count is the first line's; a line with another count is an error."""
+
+    def __init__(self, file_list, batch_size, device="cuda"):
+        self.file_list, self.batch_size, self.device = list(file_list), int(batch_size), device
+
+    def _rows(self):
+        width = None
+        for path in self.file_list:
+            with open(path, "r") as f:
+                for no, line in enumerate(f, 1):
+                    parts = line.strip().split(",")
+                    if parts == [""]:
+                        continue
+                    vals = list(map(float, parts))
+                    if len(vals) < 3 or (width is not None and len(vals) != width):
+                        raise ValueError("%s:%d has %d fields, expected %s" % (path, no, len(vals), width or "at least 3"))
+                    width = len(vals)
+                    for what, v in (("label_marital", vals[0]), ("label_income", vals[1])):
+                        if v not in (0.0, 1.0):
+                            raise ValueError("%s:%d: %s is %r, expected 0 or 1" % (path, no, what, v))
+                    yield np.array(vals[2:]).astype(np.float32), vals[1], vals[0]
+
+    def __iter__(self):
+        group = []
+        for row in self._rows():
+            group.append(row)
+            if len(group) == self.batch_size:
+                feats = torch.from_numpy(np.stack([r[0] for r in group]))
+                income = torch.tensor([[r[1]] for r in group], dtype=torch.float32)
+                marital = torch.tensor([[r[2]] for r in group], dtype=torch.float32)
+                group = []
+                yield tuple(t.to(self.device, non_blocking=True) for t in (feats, income, marital))
