@@ -1912,6 +1912,56 @@ int rec_mtl_mix_bwd(const rec_mtl_mix_desc* desc, const float* H, const float* p
 int rec_mtl_head(int64_t batch, int32_t n_tasks, const float* logits, int64_t ld, const float* label, int64_t ld_label,
                  float grad_scale, float* pred, float* cost, float* dlogits, void* stream);
 
+/* ----------------------------------------------------------------------------------------
+ * The entire-space multitask nets (models/multitask/esmm, escm2): the padded multi-field sum-pool and the entire-space
+ * head (csrc/esm_ops.hip).  float32, no atomics, no workspace; every output element is produced by one thread or one
+ * fixed-order fold, so a rerun is bit-identical.  Arguments are checked on the host before any launch (REC_EINVAL);
+ * batch == 0 returns REC_OK without a launch.
+ *
+ * rec_field_sumpool_fwd: ids int64 [batch, num_fields, max_len], packed; W [num_rows, emb_dim] with row stride
+ *   row_stride >= emb_dim.  out[b, f * emb_dim + d] = sum over l, ascending, starting from +0.0f, of W[ids[b, f, l], d];
+ *   an id equal to padding_idx is skipped (padding_idx < 0: none).  An id outside [0, num_rows) sets REC_FLAG_INDEX_OOB
+ *   in *status (status may be NULL), counts as padding, and its row is never read.  ld_out: row stride of out in floats,
+ *   0 = packed (num_fields * emb_dim); a non-zero value below the packed width is refused; columns beyond the packed
+ *   width are not touched.  float4 accesses when emb_dim, row_stride and ld_out are multiples of 4 and W and out are
+ *   16-byte aligned; the scalar form otherwise.  Limits: max_len 1..64, emb_dim 1..1024, num_fields >= 1.
+ *   There is no backward entry point: lookup i of the flattened ids takes row i / max_len of dX viewed as
+ *   [batch * num_fields, emb_dim], i.e. rec_grad_layout.div = max_len for rec_segment_partials / rec_adam_rows_all.
+ *
+ * rec_esm_head: logits [batch, 2G] (row stride ld_logit, 0 = packed), G = 2 (tasks ctr, cvr) in the modes REC_ESM_ESMM and
+ *   REC_ESM_IPW, G = 3 (ctr, cvr, imputation) in REC_ESM_DR; click, buy int64 [batch].  Per task p = softmax over its two
+ *   logits (maximum subtracted); the ESCM2 modes (IPW, DR) clip p to [1e-15, 1 - 1e-15] evaluated in float32 (the upper
+ *   bound is 1), ESMM does not.  With p1, q1, i1 column 1 of the ctr, cvr and imputation tasks, y = o = float(click), t =
+ *   float(buy), r = p1 q1 and L(x, lab) = -lab log(x + 1e-4) - (1 - lab) log(1 - x + 1e-4):
+ *     pred [batch, 2G + 2]: columns 2g, 2g + 1 task g's (clipped) softmax, the last two (1 - r, r);
+ *     cost [batch, 3]:  cost0 = L(p1, y);  cost2 = L(r, t);  cost1 = 0 (ESMM),
+ *       L(q1, t) IPS o with IPS = clip(1 / max(p1 float(N_click), 1e-6), -15, 15) float(batch)            (IPW),
+ *       i1 + e IPS + e^2 IPS with e = L(q1, t) - i1 and IPS = clip(o / max(p1, 1e-6), -15, 15)             (DR);
+ *     dlogits [batch, 2G] (NULL at inference): the gradient of grad_scale (cost0 + counterfactual_w cost1 + global_w
+ *       cost2) through the clip (passing where lo <= p <= hi) and the softmax, IPS carrying none; per task ONE value is
+ *       computed and column 0 holds its negation: dlogits[2g] == -dlogits[2g + 1] exactly.
+ *   pred, cost and dlogits are packed.  The step's loss is mean(cost0) + counterfactual_w mean(cost1) + global_w
+ *   mean(cost2), left to the caller.  click_count: int64 [1] device OUTPUT, N_click = sum click, filled first by one
+ *   workgroup (an exact integer fold) whenever it is non-null; required in the IPW mode, may be NULL otherwise.
+ * ---------------------------------------------------------------------------------------- */
+#define REC_FIELD_SUMPOOL_MAX_LEN 64
+#define REC_FIELD_SUMPOOL_MAX_DIM 1024
+#define REC_ESM_ESMM 0
+#define REC_ESM_IPW 1
+#define REC_ESM_DR 2
+typedef struct {
+  int64_t batch;
+  int32_t mode;
+  int64_t ld_logit;
+  float global_w, counterfactual_w, grad_scale;
+} rec_esm_head_desc;
+
+int rec_field_sumpool_fwd(int64_t batch, int32_t num_fields, int32_t max_len, int32_t emb_dim, int32_t row_stride,
+                          int64_t num_rows, int64_t padding_idx, const int64_t* ids, const float* W, float* out, int64_t ld_out,
+                          int32_t* status, void* stream);
+int rec_esm_head(const rec_esm_head_desc* desc, const float* logits, const int64_t* click, const int64_t* buy,
+                 int64_t* click_count, float* pred, float* cost, float* dlogits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

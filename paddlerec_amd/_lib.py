@@ -200,6 +200,16 @@ class MtlMixDesc(C.Structure):
                 ("first1", C.c_int32 * 16), ("count1", C.c_int32 * 16)]
 
 
+REC_FIELD_SUMPOOL_MAX_LEN, REC_FIELD_SUMPOOL_MAX_DIM = 64, 1024
+REC_ESM_ESMM, REC_ESM_IPW, REC_ESM_DR = 0, 1, 2
+
+
+class EsmHeadDesc(C.Structure):
+    """rec_esm_head_desc (include/recengine.h)."""
+    _fields_ = [("batch", C.c_int64), ("mode", C.c_int32), ("ld_logit", C.c_int64), ("global_w", C.c_float),
+                ("counterfactual_w", C.c_float), ("grad_scale", C.c_float)]
+
+
 class IdsGroupPlan(C.Structure):
     """rec_ids_group_plan_t (include/recengine.h)."""
     _fields_ = [("passes", C.c_int32), ("bits", C.c_int32 * 8), ("waves", C.c_int32), ("key_bytes", C.c_int32),
@@ -314,6 +324,8 @@ SIGNATURES = {
     "rec_mtl_mix_fwd": (C.c_int, [C.POINTER(MtlMixDesc), _P, _P, _P, _P, _P]),
     "rec_mtl_mix_bwd": (C.c_int, [C.POINTER(MtlMixDesc), _P, _P, _P, _I32, _P, _P, _P]),
     "rec_mtl_head": (C.c_int, [_I64, _I32, _P, _I64, _P, _I64, _F, _P, _P, _P, _P]),
+    "rec_field_sumpool_fwd": (C.c_int, [_I64, _I32, _I32, _I32, _I32, _I64, _I64, _P, _P, _P, _I64, _P, _P]),
+    "rec_esm_head": (C.c_int, [C.POINTER(EsmHeadDesc), _P, _P, _P, _P, _P, _P, _P, _P]),
     "rec_dense_fold_fwd": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P]),
     "rec_dense_fold_bwd": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _I32, _P]),
     "rec_dense_fold_fwd_full": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P]),

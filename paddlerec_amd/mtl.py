@@ -3,7 +3,7 @@ census_reader.py): the layer that runs a PLAN of expert / gate levels on the rec
 
 A plan (mmoe.py / ple.py write it from the reference's constructor and forward) is
     params:   [(name, in, out, weight constant, bias constant)] — every nn.Linear of the net in state_dict order, also the
-              ones forward() never calls
+              ones forward() never calls; in place of a constant, a callable that fills the tensor it is given
     aliases:  {second state_dict name: first} of one Linear
     levels:   [{"slots": [(expert name, input)], "gates": [(gate name, input, (first0, count0, first1, count1))]}] — the
               expert outputs of a level in the order the reference concatenates them (a SLOT is one column block of
@@ -27,7 +27,8 @@ How it runs, with the same result as the reference:
     forward() never calls is in no image: it has no gradient and never moves, as under the reference's optimizer;
   * tower_out's backward uses d z0 = -d z1 (train_step has why);
   * the head is rec_mtl_head: predictions, per-sample cost and d(logits) of (1 / B) sum cost in one pass.  The loss value
-    (sum over tasks of the batch mean) is only taken, with torch, when something reads it.
+    (sum over tasks of the batch mean) is only taken, with torch, when something reads it.  A subclass may put another
+    head in its place (_head, _loss) and ask for the features' gradient (level0_dx): escm2.py does both.
 The train step is eager (no graph capture); the only torch work on its path is allocation."""
 import math
 
@@ -151,8 +152,11 @@ class MtlLayer:
             else:                                             # never called by forward(): no gradient, no optimizer state
                 self._views["p"][n + ".weight"] = torch.empty(i, o, dtype=torch.float32, device=self.device)
                 self._views["p"][n + ".bias"] = torch.empty(o, dtype=torch.float32, device=self.device)
-            self._views["p"][n + ".weight"].fill_(float(wv))
-            self._views["p"][n + ".bias"].fill_(float(bv))
+            for view, init in ((self._views["p"][n + ".weight"], wv), (self._views["p"][n + ".bias"], bv)):
+                if callable(init):                            # an initialiser other than a constant: fills the view in place
+                    init(view)
+                else:
+                    view.fill_(float(init))
             self.params[n + ".weight"], self.params[n + ".bias"] = self._views["p"][n + ".weight"], self._views["p"][n + ".bias"]
         self.aliases = {}
         for a, n in plan.get("aliases", {}).items():
@@ -165,6 +169,7 @@ class MtlLayer:
         self.ws = self.k.Workspace(self.device)
         self.step_count = 0
         self._last = None
+        self.level0_dx = False      # True: train_step also runs level 0's dX GEMM and keeps it as self._last["dX"]
 
     # ---------------------------------------------------------------- parameters
     def _sync_copies(self, stores=STORES):
@@ -307,9 +312,7 @@ class MtlLayer:
         sv = {}
         z = self._run(x, keep=sv)
         B, T = sv["B"], self.tasks
-        if tuple(label.shape) != (B, T) or label.dtype != torch.float32:
-            raise ValueError("label must be float32 [B, %d], got %s %s" % (T, label.dtype, tuple(label.shape)))
-        pred, cost, dz = k.mtl_head(z, label, 1.0 / B)
+        pred, cost, dz = self._head(z, label, B)
         f32 = dict(dtype=torch.float32, device=self.device)
         S = self.levels[-1]["S"]
         dtop = torch.empty(B, len(self.plan["levels"][-1]["gates"]) * S, **f32)
@@ -326,6 +329,7 @@ class MtlLayer:
             da = k.gemm(dz[:, 2 * t + 1:2 * t + 2], wd, ws, trans_b=True, epilogue="relu_mask", aux0=a)
             k.linear_backward(sv["top"][:, t * S:(t + 1) * S], da, p[n + ".weight"], ws, g[n + ".weight"], g[n + ".bias"],
                               out=dtop[:, t * S:(t + 1) * S])
+        dx0 = None
         for li in reversed(range(len(self.levels))):
             lev, tp = self.levels[li], sv["tape"][li]
             S, nH = lev["S"], lev["n_slots"] * lev["S"]
@@ -346,20 +350,34 @@ class MtlLayer:
                     for col, n in im["gates"]:
                         k.bst_add(dlogits[:, col:col + n], None, out=Gi[:, c:c + n])
                         c += n
-                if li == 0:                                   # the features need no gradient: dW and db alone
+                if li == 0 and self.level0_dx:                # a subclass trains what makes the features
+                    dx0 = k.linear_backward(xi, Gi, W, ws, gW, gb)
+                elif li == 0:                                 # the features need no gradient: dW and db alone
                     k.gemm(xi, Gi, ws, trans_a=True, out=gW, b_colsum=gb)
                 else:
                     k.linear_backward(xi, Gi, W, ws, gW, gb, out=below[:, im["input"] * img.K:(im["input"] + 1) * img.K])
             dtop = below
         self._fold_copies()
-        self._last = dict(dz=dz)
+        self._last = dict(dz=dz, dX=dx0)
         for lev in self.levels:
             for im in lev["images"]:
                 f = im["img"].flat
                 k.adam_dense(f["p"], f["m"], f["v"], f["g"], self.step_count, lr, BETA1, BETA2, ADAM_EPS)
         f = self.tail.flat
         k.adam_dense(f["p"], f["m"], f["v"], f["g"], self.step_count, lr, BETA1, BETA2, ADAM_EPS)
-        return LazyLoss(cost), pred
+        return self._loss(cost), pred
+
+    def _head(self, z, label, B):
+        """The head of the step: towers' logits z [B, 2T] and the labels -> (pred, cost, dz = d(loss) / dz).  A subclass with
+        another head returns a dz with dz[:, 2t] == -dz[:, 2t + 1] exactly (the towers' backward above relies on it)."""
+        T = self.tasks
+        if tuple(label.shape) != (B, T) or label.dtype != torch.float32:
+            raise ValueError("label must be float32 [B, %d], got %s %s" % (T, label.dtype, tuple(label.shape)))
+        return self.k.mtl_head(z, label, 1.0 / B)
+
+    def _loss(self, cost):
+        """The loss object train_step returns for the head's per-sample cost."""
+        return LazyLoss(cost)
 
     def last_gradients(self):
         """The gradients of the newest train_step as {state_dict key: tensor}, for the parameters that have one."""

@@ -11,7 +11,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import (EPI, AdagradHyper, AdamHyper, CinView, DcnCrossDesc, DeepFMDesc, DinDesc, FatFFMDesc, FEFMDesc, FFMDesc, GemmBImage, GemmDesc, GemmEpilogueArgs, GradLayout,
+from ._lib import (EPI, AdagradHyper, AdamHyper, CinView, DcnCrossDesc, DeepFMDesc, DinDesc, EsmHeadDesc, FatFFMDesc, FEFMDesc, FFMDesc, GemmBImage, GemmDesc, GemmEpilogueArgs, GradLayout,
                    GradSrc, LazyInit, MtlMixDesc, MultislotDesc, PsAccessor, PsLayout, RecError, check)
 
 _recorder = None        # paddlerec_amd.plan.CallPlan while a step is being recorded
@@ -2537,6 +2537,57 @@ def mtl_head(logits, label, grad_scale=1.0, want_grad=True):
     dl = torch.empty(B, 2 * T, **f32) if want_grad else None
     check(lib().rec_mtl_head(B, T, _p(logits), ld, _p(label), ldl, float(grad_scale), _p(pred), _p(cost), _p(dl), _stream()),
           "rec_mtl_head")
+    return pred, cost, dl
+
+
+# ------------------------------------------------------------------ entire-space multitask (esmm, escm2): field pool, head
+ESM_MODES = {"ESMM": _lib.REC_ESM_ESMM, "IPW": _lib.REC_ESM_IPW, "DR": _lib.REC_ESM_DR}
+
+
+def field_sumpool_fwd(ids, W, padding_idx, out=None, status=None):
+    """Padded multi-field sum-pool (rec_field_sumpool_fwd): ids [B, F, L] int64, W [N, D] -> out [B, F*D] with
+    out[b, f*D:(f+1)*D] = sum_l W[ids[b, f, l]], ids equal to padding_idx (None: no padding id) skipped; an id outside
+    [0, N) is flagged in status, skipped and never read.  out: a [B, F*D] view with a row stride (allocated packed when
+    None).  -> (out, status)."""
+    _chk(ids, torch.int64, "ids")
+    if ids.dim() != 3:
+        raise RecError("ids must be [B, F, L], got %s" % (tuple(ids.shape),))
+    B, F, L = ids.shape
+    D, rs = _chk_table(W, "W")
+    if W.dim() != 2:
+        raise RecError("W must be [N, D]")
+    if out is None:
+        out = torch.empty(B, F * D, dtype=torch.float32, device=W.device)
+    ld = _mtl_view(out, B, F * D, "out")
+    if status is None:
+        status = new_status(W.device)
+    check(lib().rec_field_sumpool_fwd(B, F, L, D, rs, W.shape[0], -1 if padding_idx is None else int(padding_idx), _p(ids),
+                                      _p(W), _p(out), ld, _p(status), _stream()), "rec_field_sumpool_fwd")
+    return out, status
+
+
+def esm_head(logits, click, buy, mode, global_w=1.0, counterfactual_w=0.0, grad_scale=1.0, want_grad=True, click_count=None):
+    """The entire-space head (rec_esm_head).  logits [B, 2G] float32 view with a row stride (G = 3 in mode "DR", else 2),
+    click / buy [B] int64, mode "ESMM" | "IPW" | "DR".  -> (pred [B, 2G+2], cost [B, 3], dlogits [B, 2G] = d(grad_scale *
+    (cost0 + counterfactual_w cost1 + global_w cost2)) or None).  click_count: int64 [1] that receives sum(click); when None
+    it is allocated here in the IPW mode, the only one that reads it, and the other modes skip the count."""
+    if mode not in ESM_MODES:
+        raise RecError("esm_head: unknown mode %r (ESMM, IPW, DR)" % (mode,))
+    G = 3 if mode == "DR" else 2
+    B = logits.shape[0]
+    ld = _mtl_view(logits, B, 2 * G, "logits")
+    _chk(click, torch.int64, "click", (B,))
+    _chk(buy, torch.int64, "buy", (B,))
+    dev = logits.device
+    if click_count is None and mode == "IPW":
+        click_count = torch.empty(1, dtype=torch.int64, device=dev)
+    _chk(click_count, torch.int64, "click_count", (1,))
+    pred = torch.empty(B, 2 * G + 2, dtype=torch.float32, device=dev)
+    cost = torch.empty(B, 3, dtype=torch.float32, device=dev)
+    dl = torch.empty(B, 2 * G, dtype=torch.float32, device=dev) if want_grad else None
+    d = EsmHeadDesc(B, ESM_MODES[mode], ld, float(global_w), float(counterfactual_w), float(grad_scale))
+    check(lib().rec_esm_head(C.byref(d), _p(logits), _p(click), _p(buy), _p(click_count), _p(pred), _p(cost), _p(dl), _stream()),
+          "rec_esm_head")
     return pred, cost, dl
 
 

@@ -632,3 +632,49 @@ class CensusReader:
                 marital = torch.tensor([[r[2]] for r in group], dtype=torch.float32)
                 group = []
                 yield tuple(t.to(self.device, non_blocking=True) for t in (feats, income, marital))
+
+
+class AliCCPReader:
+    """models/multitask/esmm/esmm_reader.py and escm2/escm_reader.py RecDataset (the two files are identical) with the
+    batching of the other readers (drop_last over the concatenation of the files).  A line is `_, ctr, ctcvr, _,
+    field:feat, ...`; the features of the 23 fields below are kept in line order, every other field is dropped, and each
+    field is cut to max_len ids (hyper_parameters.max_len, default 3) or padded with 0.  Yields (ids [B, 23, max_len] i64,
+    click [B] i64, buy [B] i64) on `device`: ids[:, f, :] is the reference's f-th per-field array."""
+    FIELDS = ("101", "109_14", "110_14", "127_14", "150_14", "121", "122", "124", "125", "126", "127", "128", "129", "205",
+              "206", "207", "210", "216", "508", "509", "702", "853", "301")
+
+    def __init__(self, file_list, batch_size, device="cuda", max_len=3):
+        self.file_list, self.batch_size, self.device, self.max_len = list(file_list), int(batch_size), device, int(max_len)
+        self.index = {f: i for i, f in enumerate(self.FIELDS)}
+
+    def _rows(self):
+        L = self.max_len
+        for path in self.file_list:
+            with open(path, "r") as f:
+                for no, line in enumerate(f, 1):
+                    parts = line.strip().split(",")
+                    if parts == [""]:
+                        continue
+                    if len(parts) < 4:
+                        raise ValueError("%s:%d has %d fields, expected at least 4" % (path, no, len(parts)))
+                    ids, fill = np.zeros((len(self.FIELDS), L), np.int64), [0] * len(self.FIELDS)
+                    for elem in parts[4:]:
+                        field, _, feat = elem.strip().partition(":")
+                        i = self.index.get(field)
+                        if i is None:
+                            continue
+                        if fill[i] < L:
+                            ids[i, fill[i]] = int(feat)
+                        fill[i] += 1
+                    yield ids, int(parts[1]), int(parts[2])
+
+    def __iter__(self):
+        group = []
+        for row in self._rows():
+            group.append(row)
+            if len(group) == self.batch_size:
+                ids = torch.from_numpy(np.stack([r[0] for r in group]))
+                click = torch.tensor([r[1] for r in group], dtype=torch.int64)
+                buy = torch.tensor([r[2] for r in group], dtype=torch.int64)
+                group = []
+                yield tuple(t.to(self.device, non_blocking=True) for t in (ids, click, buy))
