@@ -1962,6 +1962,77 @@ int rec_field_sumpool_fwd(int64_t batch, int32_t num_fields, int32_t max_len, in
 int rec_esm_head(const rec_esm_head_desc* desc, const float* logits, const int64_t* click, const int64_t* buy,
                  int64_t* click_count, float* pred, float* cost, float* dlogits, void* stream);
 
+/* ----------------------------------------------------------------------------------------
+ * AITM (models/multitask/aitm): the per-field gather over tables of unequal size, the adaptive information transfer (AIT)
+ * block, the coupled two-task head and the AUC histogram with more buckets than LDS holds (csrc/aitm_ops.hip).  float32;
+ * no entry point takes a workspace; no float atomics; every output element has one writer and every cross-lane sum is a
+ * fixed-order butterfly, so a rerun is bit-identical (the wide histogram adds INTEGERS atomically: exact in any order).
+ * Arguments are checked on the host before any launch (REC_EINVAL); batch == 0 returns REC_OK without a launch after
+ * those checks.  A row stride ld_* of 0 means packed; a non-zero value below the packed width is refused; columns beyond
+ * the packed width are not touched.  The float4 form runs when the widths and strides are multiples of 4 and the row
+ * pointers are 16-byte aligned, the scalar form otherwise (same order of operations, same result).
+ *
+ * rec_field_gather_fwd: ids int64 [batch, num_fields], packed; field f owns the rows [field_begin[f], field_begin[f + 1])
+ *   of W (row stride row_stride >= emb_dim); field_begin int64 [num_fields + 1] is DEVICE memory.
+ *   out[b, f * emb_dim + d] = W[field_begin[f] + ids[b, f], d].  There is no padding id: id 0 is a row like any other.
+ *   An id outside [0, field_begin[f + 1] - field_begin[f]) — also one that is still inside the whole buffer, i.e. in a
+ *   neighbouring field's rows — sets REC_FLAG_INDEX_OOB in *status (status may be NULL), is never read, and writes a zero
+ *   row.  rows_out (int64 [batch * num_fields], may be NULL) receives the global row field_begin[f] + id, or -1 for such an
+ *   id: rec_ids_group drops a negative id (it counts it as out of range: the flag is set there too, no row is touched),
+ *   so rows_out with padding_idx = -1 and num_rows = field_begin[num_fields] is the grouping of the backward
+ *   (rec_grad_layout.div = 1 over dX viewed as [batch * num_fields, emb_dim]).  emb_dim 1..1024, num_fields >= 1.
+ *
+ * rec_ait_fwd: QKV [batch * tokens, 3 dim] (row stride ld_qkv), row b * tokens + t = Q_t | K_t | V_t of sample b.
+ *   s_t = <Q_t, K_t> / sqrt(dim) (each token's OWN Q and K: aitm/net.py:57), a = softmax over the tokens (maximum
+ *   subtracted), out[b] = sum_t a_t V_t, t ascending (out [batch, dim], row stride ld_out); prob [batch, tokens] packed
+ *   receives a.  tokens 1..8, dim 1..256.
+ * rec_ait_bwd: the same QKV and prob, d_out [batch, dim] (ld_dout) -> dQKV [batch * tokens, 3 dim] (ld_dqkv):
+ *   dV_t = a_t d_out, da_t = <d_out, V_t>, ds_t = a_t (da_t - sum_u a_u da_u), dQ_t = ds_t K_t / sqrt(dim),
+ *   dK_t = ds_t Q_t / sqrt(dim); with tokens == 1, dQ and dK are exactly zero.  Weight and input gradients are GEMMs over
+ *   dQKV (rec_gemm_f32_pair); nothing is reduced over the batch here.
+ *
+ * rec_aitm_head: tower_click, ait [batch, dim] (ld_click, ld_ait); w_click, w_conv [dim]; b_click, b_conv [1]; click, buy
+ *   int64 [batch].  pCTR = sigmoid(<tower_click, w_click> + b_click), pCVR = sigmoid(<ait, w_conv> + b_conv);
+ *     pred [batch, 2]: (pCTR, pCVR);
+ *     cost [batch, 3]: BCE(pCTR, click), BCE(pCVR, buy), max(pCVR - pCTR, 0) with
+ *       BCE(p, y) = -(y max(log p, -100) + (1 - y) max(log(1 - p), -100));
+ *     dz [batch, 2] (NULL at inference): d / d(logit) of grad_scale (cost0 + cost1) + constraint_w cost2, as the chain
+ *       (grad_scale (p - y) / max(p (1 - p), 1e-12) -/+ constraint_w [pCVR > pCTR]) p (1 - p): the hinge term is NOT scaled
+ *       by grad_scale (the reference sums it over the batch and averages the BCE terms) and passes only where pCVR > pCTR
+ *       strictly.
+ *   pred, cost and dz are packed.  The step's loss, mean(cost0) + mean(cost1) + constraint_w sum(cost2), is left to the
+ *   caller.  dim 1..4096.
+ *
+ * rec_auc_histogram_wide: rec_auc_histogram's buckets (bucket = clamp(int(pred * num_thresholds), 0, num_thresholds);
+ *   stat_pos / stat_neg int64 [num_thresholds + 1] += 1) for 1 <= num_thresholds <= 2^24, accumulated straight into global
+ *   memory with 64-bit integer atomics; pred[i] is read at pred[i * ld_pred] (0 = packed, 1), so a column of pred
+ *   [batch, 2] needs no copy.
+ * ---------------------------------------------------------------------------------------- */
+#define REC_FIELD_GATHER_MAX_DIM 1024
+#define REC_AIT_MAX_TOKENS 8
+#define REC_AIT_MAX_DIM 256
+#define REC_AITM_HEAD_MAX_DIM 4096
+#define REC_AUC_WIDE_MAX_THRESHOLDS (1 << 24)
+typedef struct {
+  int64_t batch;
+  int32_t dim;
+  int64_t ld_click, ld_ait;
+  float constraint_w, grad_scale;
+} rec_aitm_head_desc;
+
+int rec_field_gather_fwd(int64_t batch, int32_t num_fields, int32_t emb_dim, int32_t row_stride, const int64_t* field_begin,
+                         const int64_t* ids, const float* W, float* out, int64_t ld_out, int64_t* rows_out, int32_t* status,
+                         void* stream);
+int rec_ait_fwd(int64_t batch, int32_t tokens, int32_t dim, const float* QKV, int64_t ld_qkv, float* out, int64_t ld_out,
+                float* prob, void* stream);
+int rec_ait_bwd(int64_t batch, int32_t tokens, int32_t dim, const float* QKV, int64_t ld_qkv, const float* prob,
+                const float* d_out, int64_t ld_dout, float* dQKV, int64_t ld_dqkv, void* stream);
+int rec_aitm_head(const rec_aitm_head_desc* desc, const float* tower_click, const float* ait, const float* w_click,
+                  const float* b_click, const float* w_conv, const float* b_conv, const int64_t* click, const int64_t* buy,
+                  float* pred, float* cost, float* dz, void* stream);
+int rec_auc_histogram_wide(int64_t batch, const float* pred, int64_t ld_pred, const int64_t* label, int32_t num_thresholds,
+                           int64_t* stat_pos, int64_t* stat_neg, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -210,6 +210,16 @@ class EsmHeadDesc(C.Structure):
                 ("counterfactual_w", C.c_float), ("grad_scale", C.c_float)]
 
 
+REC_FIELD_GATHER_MAX_DIM, REC_AIT_MAX_TOKENS, REC_AIT_MAX_DIM, REC_AITM_HEAD_MAX_DIM = 1024, 8, 256, 4096
+REC_AUC_WIDE_MAX_THRESHOLDS = 1 << 24
+
+
+class AitmHeadDesc(C.Structure):
+    """rec_aitm_head_desc (include/recengine.h)."""
+    _fields_ = [("batch", C.c_int64), ("dim", C.c_int32), ("ld_click", C.c_int64), ("ld_ait", C.c_int64),
+                ("constraint_w", C.c_float), ("grad_scale", C.c_float)]
+
+
 class IdsGroupPlan(C.Structure):
     """rec_ids_group_plan_t (include/recengine.h)."""
     _fields_ = [("passes", C.c_int32), ("bits", C.c_int32 * 8), ("waves", C.c_int32), ("key_bytes", C.c_int32),
@@ -326,6 +336,11 @@ SIGNATURES = {
     "rec_mtl_head": (C.c_int, [_I64, _I32, _P, _I64, _P, _I64, _F, _P, _P, _P, _P]),
     "rec_field_sumpool_fwd": (C.c_int, [_I64, _I32, _I32, _I32, _I32, _I64, _I64, _P, _P, _P, _I64, _P, _P]),
     "rec_esm_head": (C.c_int, [C.POINTER(EsmHeadDesc), _P, _P, _P, _P, _P, _P, _P, _P]),
+    "rec_field_gather_fwd": (C.c_int, [_I64, _I32, _I32, _I32, _P, _P, _P, _P, _I64, _P, _P, _P]),
+    "rec_ait_fwd": (C.c_int, [_I64, _I32, _I32, _P, _I64, _P, _I64, _P, _P]),
+    "rec_ait_bwd": (C.c_int, [_I64, _I32, _I32, _P, _I64, _P, _P, _I64, _P, _I64, _P]),
+    "rec_aitm_head": (C.c_int, [C.POINTER(AitmHeadDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "rec_auc_histogram_wide": (C.c_int, [_I64, _P, _I64, _P, _I32, _P, _P, _P]),
     "rec_dense_fold_fwd": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P]),
     "rec_dense_fold_bwd": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _I32, _P]),
     "rec_dense_fold_fwd_full": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P]),

@@ -11,7 +11,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import (EPI, AdagradHyper, AdamHyper, CinView, DcnCrossDesc, DeepFMDesc, DinDesc, EsmHeadDesc, FatFFMDesc, FEFMDesc, FFMDesc, GemmBImage, GemmDesc, GemmEpilogueArgs, GradLayout,
+from ._lib import (EPI, AdagradHyper, AdamHyper, AitmHeadDesc, CinView, DcnCrossDesc, DeepFMDesc, DinDesc, EsmHeadDesc, FatFFMDesc, FEFMDesc, FFMDesc, GemmBImage, GemmDesc, GemmEpilogueArgs, GradLayout,
                    GradSrc, LazyInit, MtlMixDesc, MultislotDesc, PsAccessor, PsLayout, RecError, check)
 
 _recorder = None        # paddlerec_amd.plan.CallPlan while a step is being recorded
@@ -2589,6 +2589,113 @@ def esm_head(logits, click, buy, mode, global_w=1.0, counterfactual_w=0.0, grad_
     check(lib().rec_esm_head(C.byref(d), _p(logits), _p(click), _p(buy), _p(click_count), _p(pred), _p(cost), _p(dl), _stream()),
           "rec_esm_head")
     return pred, cost, dl
+
+
+# ------------------------------------------------------------------ AITM: per-field gather, AIT block, head, wide AUC buckets
+def field_gather_fwd(ids, W, field_begin, out=None, rows_out=None, status=None):
+    """One lookup per field over tables of unequal size kept in one buffer (rec_field_gather_fwd): ids [B, F] int64, W
+    [sum vocab, D], field_begin [F + 1] int64 on the device -> out [B, F*D] with out[b, f*D:(f+1)*D] = W[field_begin[f] +
+    ids[b, f]].  There is no padding id.  An id outside ITS field's [0, vocab_f) is flagged in status, never read, gives a
+    zero row and -1 in rows_out; otherwise rows_out [B*F] int64 holds the global row (allocated here when None: it is what
+    ids_group(rows_out, sum vocab, None, ...) groups for the backward).  out: a [B, F*D] view with a row stride (allocated
+    packed when None).  -> (out, rows_out, status)."""
+    _chk(ids, torch.int64, "ids")
+    if ids.dim() != 2:
+        raise RecError("ids must be [B, F], got %s" % (tuple(ids.shape),))
+    B, F = ids.shape
+    D, rs = _chk_table(W, "W")
+    if W.dim() != 2:
+        raise RecError("W must be [N, D]")
+    _chk(field_begin, torch.int64, "field_begin", (F + 1,))
+    if out is None:
+        out = torch.empty(B, F * D, dtype=torch.float32, device=W.device)
+    ld = _mtl_view(out, B, F * D, "out")
+    if rows_out is None:
+        rows_out = torch.empty(B * F, dtype=torch.int64, device=W.device)
+    _chk(rows_out, torch.int64, "rows_out", (B * F,))
+    if status is None:
+        status = new_status(W.device)
+    check(lib().rec_field_gather_fwd(B, F, D, rs, _p(field_begin), _p(ids), _p(W), _p(out), ld, _p(rows_out), _p(status),
+                                     _stream()), "rec_field_gather_fwd")
+    return out, rows_out, status
+
+
+def _ait_args(QKV, tokens, what):
+    T = int(tokens)
+    if QKV.dim() != 2 or QKV.shape[1] % 3 or QKV.shape[0] % max(T, 1):
+        raise RecError("%s: QKV must be [B * tokens, 3 * dim], got %s with tokens %d" % (what, tuple(QKV.shape), T))
+    B, d = QKV.shape[0] // max(T, 1), QKV.shape[1] // 3
+    return B, T, d, _mtl_view(QKV, B * T, 3 * d, "QKV")
+
+
+def ait_fwd(QKV, tokens, out=None, prob=None):
+    """The adaptive information transfer block (rec_ait_fwd): QKV [B * tokens, 3 dim], a float32 view with a row stride whose
+    row b * tokens + t is Q_t | K_t | V_t of sample b.  a = softmax_t(<Q_t, K_t> / sqrt(dim)), out[b] = sum_t a_t V_t.
+    -> (out [B, dim] (a view with a row stride when given), prob [B, tokens])."""
+    B, T, d, ld = _ait_args(QKV, tokens, "ait_fwd")
+    f32 = dict(dtype=torch.float32, device=QKV.device)
+    if out is None:
+        out = torch.empty(B, d, **f32)
+    if prob is None:
+        prob = torch.empty(B, T, **f32)
+    _chk(prob, torch.float32, "prob", (B, T))
+    check(lib().rec_ait_fwd(B, T, d, _p(QKV), ld, _p(out), _mtl_view(out, B, d, "out"), _p(prob), _stream()), "rec_ait_fwd")
+    return out, prob
+
+
+def ait_bwd(QKV, prob, d_out, tokens, out=None):
+    """Backward of ait_fwd (rec_ait_bwd): d_out [B, dim] -> dQKV [B * tokens, 3 dim] in QKV's column layout (a view with a
+    row stride when given).  With one token, dQ and dK are exactly zero."""
+    B, T, d, ld = _ait_args(QKV, tokens, "ait_bwd")
+    _chk(prob, torch.float32, "prob", (B, T))
+    if out is None:
+        out = torch.empty(B * T, 3 * d, dtype=torch.float32, device=QKV.device)
+    check(lib().rec_ait_bwd(B, T, d, _p(QKV), ld, _p(prob), _p(d_out), _mtl_view(d_out, B, d, "d_out"), _p(out),
+                            _mtl_view(out, B * T, 3 * d, "dQKV"), _stream()), "rec_ait_bwd")
+    return out
+
+
+def aitm_head(tower_click, ait, w_click, b_click, w_conv, b_conv, click, buy, constraint_w=0.6, grad_scale=1.0, want_grad=True):
+    """AITM's coupled head (rec_aitm_head): tower_click, ait [B, dim] float32 views with a row stride; w_click, w_conv [dim]
+    (or [dim, 1]) and b_click, b_conv [1] contiguous; click, buy [B] int64.  -> (pred [B, 2] = pCTR | pCVR, cost [B, 3] =
+    BCE(pCTR, click) | BCE(pCVR, buy) | max(pCVR - pCTR, 0), dz [B, 2] = d(grad_scale (cost0 + cost1) + constraint_w cost2) by
+    the two logits, or None)."""
+    B, d = tower_click.shape
+    ldc, lda = _mtl_view(tower_click, B, d, "tower_click"), _mtl_view(ait, B, d, "ait")
+    for t, n in ((w_click, "w_click"), (w_conv, "w_conv")):
+        _chk(t, torch.float32, n)
+        if t.numel() != d:
+            raise RecError("%s has %d elements, expected %d" % (n, t.numel(), d))
+    for t, n in ((b_click, "b_click"), (b_conv, "b_conv")):
+        _chk(t, torch.float32, n)
+        if t.numel() != 1:
+            raise RecError("%s must hold one element" % n)
+    _chk(click, torch.int64, "click", (B,))
+    _chk(buy, torch.int64, "buy", (B,))
+    f32 = dict(dtype=torch.float32, device=tower_click.device)
+    pred, cost = torch.empty(B, 2, **f32), torch.empty(B, 3, **f32)
+    dz = torch.empty(B, 2, **f32) if want_grad else None
+    desc = AitmHeadDesc(B, d, ldc, lda, float(constraint_w), float(grad_scale))
+    check(lib().rec_aitm_head(C.byref(desc), _p(tower_click), _p(ait), _p(w_click), _p(b_click), _p(w_conv), _p(b_conv),
+                              _p(click), _p(buy), _p(pred), _p(cost), _p(dz), _stream()), "rec_aitm_head")
+    return pred, cost, dz
+
+
+def auc_histogram_wide(pred, label, stat_pos, stat_neg, num_thresholds=100000):
+    """auc_histogram's buckets for any 1 <= num_thresholds <= 2^24 (rec_auc_histogram_wide: integer global atomics instead of
+    LDS histograms).  pred: float32 [B], or a column of a 2-D tensor (its element stride is passed on: no copy)."""
+    _dev(pred, torch.float32, "pred")
+    if pred.dim() != 1:
+        raise RecError("pred must be [B] (a column view is fine), got %s" % (tuple(pred.shape),))
+    B = pred.shape[0]
+    ld = pred.stride(0) if B > 1 else 1
+    if ld < 1:
+        raise RecError("pred must have a positive stride")
+    _chk(label, torch.int64, "label", (B,))
+    _chk(stat_pos, torch.int64, "stat_pos", (num_thresholds + 1,))
+    _chk(stat_neg, torch.int64, "stat_neg", (num_thresholds + 1,))
+    check(lib().rec_auc_histogram_wide(B, _p(pred), ld, _p(label), int(num_thresholds), _p(stat_pos), _p(stat_neg),
+                                       _stream()), "rec_auc_histogram_wide")
 
 
 # ------------------------------------------------------------------ xDeepFM CIN (the passes around the GEMM)

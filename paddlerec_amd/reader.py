@@ -678,3 +678,36 @@ class AliCCPReader:
                 buy = torch.tensor([r[2] for r in group], dtype=torch.int64)
                 group = []
                 yield tuple(t.to(self.device, non_blocking=True) for t in (ids, click, buy))
+
+
+class AitmReader:
+    """models/multitask/aitm/aitm_reader.py RecDataset with the batching of the other readers (drop_last).  As the reference,
+    it reads ONLY file_list[0] and skips that file's first line, the header `click,purchase,<18 feature names>`; every other
+    line is comma-separated integers: click, purchase, then one id per field in the header's (= the config's) order.  Yields
+    (ids [B, F] i64, click [B] i64, buy [B] i64) on `device`: ids[:, f] is the reference's f-th feature tensor."""
+
+    def __init__(self, file_list, batch_size, device="cuda"):
+        self.file_list, self.batch_size, self.device = list(file_list), int(batch_size), device
+        self.feature_names = []
+
+    def _rows(self):
+        path = self.file_list[0]
+        with open(path, "r") as f:
+            self.feature_names = f.readline().strip().split(",")[2:]
+            for no, line in enumerate(f, 2):
+                parts = line.strip().split(",")
+                if parts == [""]:
+                    continue
+                vals = [int(v) for v in parts]
+                if len(vals) != 2 + len(self.feature_names):
+                    raise ValueError("%s:%d has %d fields, expected %d" % (path, no, len(vals), 2 + len(self.feature_names)))
+                yield vals
+
+    def __iter__(self):
+        group = []
+        for row in self._rows():
+            group.append(row)
+            if len(group) == self.batch_size:
+                a = torch.tensor(group, dtype=torch.int64)
+                group = []
+                yield tuple(t.contiguous().to(self.device, non_blocking=True) for t in (a[:, 2:], a[:, 0], a[:, 1]))

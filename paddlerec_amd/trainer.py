@@ -10,7 +10,7 @@ What differs by construction: a batch never becomes 28 per-sample NumPy arrays (
 [B,26] / [B,13] device tensors), `loss.backward(); optimizer.step()` is the explicit `train_step` chain of the
 host mirrors, and the AUC buckets stay on the device (read back only when a log line prints them).
 
-    python -m paddlerec_amd.trainer -m <config.yaml> [--model deepfm|fm|ffm|deepfefm|fat_deepffm|wide_deep|dnn|dcn|dcn_v2|gatenet|flen|autofis|din|dien|dmr|bst|xdeepfm|dlrm|mmoe|ple|esmm|escm2] [-o runner.epochs=1 ...] [--infer]
+    python -m paddlerec_amd.trainer -m <config.yaml> [--model deepfm|fm|ffm|deepfefm|fat_deepffm|wide_deep|dnn|dcn|dcn_v2|gatenet|flen|autofis|din|dien|dmr|bst|xdeepfm|dlrm|mmoe|ple|esmm|escm2|aitm] [-o runner.epochs=1 ...] [--infer]
     python -m torch.distributed.run --nproc-per-node G -m paddlerec_amd.trainer -m <config.yaml>     # collective mode
 """
 import argparse
@@ -25,7 +25,7 @@ from . import checkpoint
 logger = logging.getLogger("paddlerec_amd.trainer")
 
 MODELS = ("deepfm", "fm", "ffm", "deepfefm", "fat_deepffm", "wide_deep", "dnn", "dcn", "dcn_v2", "gatenet", "flen", "autofis",
-          "din", "dien", "dmr", "bst", "xdeepfm", "dlrm", "mmoe", "ple", "esmm", "escm2")
+          "din", "dien", "dmr", "bst", "xdeepfm", "dlrm", "mmoe", "ple", "esmm", "escm2", "aitm")
 
 
 # ------------------------------------------------------------------------------------ configuration
@@ -116,6 +116,8 @@ def _dygraph_model(name):
         from .esmm import DygraphModel
     elif name == "escm2":
         from .escm2 import DygraphModel
+    elif name == "aitm":
+        from .aitm import DygraphModel
     else:
         raise ValueError("unknown model %r (known: %s)" % (name, ", ".join(MODELS)))
     return DygraphModel()
@@ -154,6 +156,8 @@ def create_data_loader(config, model, device, mode="train", shard=None):
         return lambda: iter(reader.CensusReader(files, bs, device))
     if model in ("esmm", "escm2"):
         return lambda: iter(reader.AliCCPReader(files, bs, device, max_len=config.get("hyper_parameters.max_len", 3)))
+    if model == "aitm":
+        return lambda: iter(reader.AitmReader(files, bs, device))
     if model == "flen":
         return lambda: iter(reader.AvazuReader(files, bs, device, shard=shard))
     if model == "autofis":
@@ -319,7 +323,7 @@ def _apply_optimizer_config(config, model, dy_model):
         logger.info("bst, kept as the reference writes it: %s; preprocess_cmd=%r postprocess_cmd=%r, Dropout(%.2f) with "
                     "the engine's counter-based masks (seed %d)", QUIRKS, dy_model.preprocess_cmd, dy_model.postprocess_cmd,
                     dy_model.dropout_rate, dy_model.dropout_seed)
-    if model in ("mmoe", "ple", "esmm", "escm2"):
+    if model in ("mmoe", "ple", "esmm", "escm2", "aitm"):
         import importlib
         logger.info("%s, kept as the reference writes it: %s", model, importlib.import_module("." + model, __package__).QUIRKS)
         if model == "ple":
