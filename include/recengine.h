@@ -2033,6 +2033,65 @@ int rec_aitm_head(const rec_aitm_head_desc* desc, const float* tower_click, cons
 int rec_auc_histogram_wide(int64_t batch, const float* pred, int64_t ld_pred, const int64_t* label, int32_t num_thresholds,
                            int64_t* stat_pos, int64_t* stat_neg, void* stream);
 
+/* ----------------------------------------------------------------------------------------
+ * MIND (models/recall/mind): the capsule routing, the label-aware attention and the sampled-softmax head
+ * (csrc/mind_ops.hip).  float32; no entry point takes a workspace; no float atomics; every output element has one writer
+ * and every cross-lane sum is a fixed-order butterfly, so a rerun is bit-identical.  Arguments are checked on the host
+ * before any launch (REC_EINVAL); batch == 0 returns REC_OK without a launch after those checks.  A row stride ld_* of 0
+ * means packed; a non-zero value below the packed width is refused; columns beyond the packed width are not touched.
+ *
+ * rec_mind_routing_fwd: net.py:178-234.  low [batch * seq_len_max, hidden] (row stride ld_low; row b * seq_len_max + t):
+ *   the history embeddings times bilinear_mapping_matrix, a GEMM of the caller.  seq_len int64 [batch]; position t of
+ *   sample b is valid where t < seq_len[b] (0 or less: none; seq_len_max or more: all).  routing_logits [k_max, seq_len_max]
+ *   is shared by the batch and only read.  With B = routing_logits, iters - 1 times:
+ *     W = softmax over t of where(valid, B, -2^32 + 1);  Z = W x low;  caps = squash(Z);  B += low x caps^T (every t, the
+ *     padded ones too);   squash(Z) = Z n2 / (1 + n2) / sqrt(n2 + 1e-8), n2 = |Z|^2;
+ *   then W = softmax over the k_max CAPSULES of where(valid, B, -2^32 + 1) (net.py:226 takes axis 1): a padded position
+ *   gets exactly 1 / k_max on every capsule and contributes whatever low holds there.  Outputs, packed: W [batch, k_max,
+ *   seq_len_max], Z = W x low [batch, k_max, hidden], caps = squash(Z).  One launch; low[b] is read once and kept in LDS.
+ *   seq_len_max 1..64, k_max 1..8, hidden 1..128, iters 1..8 (iters == 1: only the final softmax).
+ * rec_mind_routing_bwd: W is a constant of the backward (B and the inner rounds sit behind stop_gradient), so from d_caps
+ *   [batch, k_max, hidden], Z and W: dZ = f d_caps + 2 f'(n2) <Z, d_caps> Z with f the squash factor, and
+ *   d_low[b * seq_len_max + t] = sum_k W[b, k, t] dZ[b, k] (row stride ld_dlow).  routing_logits has no gradient.
+ *
+ * rec_mind_label_attn_fwd: net.py:284-297.  caps2 [batch * k_max, hidden] (ld_caps), target [batch, hidden] (ld_target):
+ *   s_k = pow(<caps2_k, target>, pow_p) (pow_p == 1 takes no pow), attn = softmax over k (packed [batch, k_max]),
+ *   user = sum_k attn_k caps2_k ([batch, hidden], ld_user).  There is no capsule mask.
+ * rec_mind_label_attn_bwd: d_user [batch, hidden] -> d_caps2 [batch * k_max, hidden] and d_target [batch, hidden].
+ *
+ * rec_mind_ssm_head: net.py:63-113 after the gathers.  user, true_w [batch, hidden] (ld_user, ld_true), true_b [batch],
+ *   S [batch, n_sample] (ld_s) = user x sample_w^T from the caller's GEMM, sample_b [n_sample], labels int64 [batch],
+ *   neg int64 [n_sample], logq_true [batch], logq_neg [n_sample]:
+ *     x_0 = <user, true_w> + true_b - logq_true;  x_j = (labels[b] == neg[j] ? -1e30 : S[b, j] + sample_b[j]) - logq_neg[j]
+ *   (the accidental-hit mask BEFORE the log_q subtraction), loss[b] = logsumexp(x) - x_0 with the maximum subtracted,
+ *   S[b, j] <- grad_scale softmax(x)_j IN PLACE (exactly 0 at a hit) and d_true[b] = grad_scale (softmax(x)_0 - 1).
+ *   The true column's two row scalings, each [batch, hidden] and each may be NULL: d_true_w = d_true user (ld_dtw), the
+ *   gradient of the gathered true rows, and d_user0 = d_true true_w (ld_du0), the term of d(user) that the caller's
+ *   dS x sample_w GEMM adds to (REC_EPI_ADD).
+ *   hidden 1..1024, n_sample 1..65536.
+ * ---------------------------------------------------------------------------------------- */
+#define REC_MIND_MAX_T 64
+#define REC_MIND_MAX_K 8
+#define REC_MIND_MAX_H 128
+#define REC_MIND_MAX_ITERS 8
+#define REC_MIND_HEAD_MAX_DIM 1024
+#define REC_MIND_MAX_NEG 65536
+
+int rec_mind_routing_fwd(int64_t batch, int32_t seq_len_max, int32_t k_max, int32_t hidden, int32_t iters, const float* low,
+                         int64_t ld_low, const int64_t* seq_len, const float* routing_logits, float* W, float* Z, float* caps,
+                         void* stream);
+int rec_mind_routing_bwd(int64_t batch, int32_t seq_len_max, int32_t k_max, int32_t hidden, const float* d_caps, const float* Z,
+                         const float* W, float* d_low, int64_t ld_dlow, void* stream);
+int rec_mind_label_attn_fwd(int64_t batch, int32_t k_max, int32_t hidden, float pow_p, const float* caps2, int64_t ld_caps,
+                            const float* target, int64_t ld_target, float* user, int64_t ld_user, float* attn, void* stream);
+int rec_mind_label_attn_bwd(int64_t batch, int32_t k_max, int32_t hidden, float pow_p, const float* caps2, int64_t ld_caps,
+                            const float* target, int64_t ld_target, const float* attn, const float* d_user, int64_t ld_duser,
+                            float* d_caps2, int64_t ld_dcaps, float* d_target, int64_t ld_dtarget, void* stream);
+int rec_mind_ssm_head(int64_t batch, int32_t hidden, int32_t n_sample, const float* user, int64_t ld_user, const float* true_w,
+                      int64_t ld_true, const float* true_b, float* S, int64_t ld_s, const float* sample_b, const int64_t* labels,
+                      const int64_t* neg, const float* logq_true, const float* logq_neg, float grad_scale, float* loss,
+                      float* d_true, float* d_true_w, int64_t ld_dtw, float* d_user0, int64_t ld_du0, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -220,6 +220,10 @@ class AitmHeadDesc(C.Structure):
                 ("constraint_w", C.c_float), ("grad_scale", C.c_float)]
 
 
+REC_MIND_MAX_T, REC_MIND_MAX_K, REC_MIND_MAX_H, REC_MIND_MAX_ITERS = 64, 8, 128, 8
+REC_MIND_HEAD_MAX_DIM, REC_MIND_MAX_NEG = 1024, 65536
+
+
 class IdsGroupPlan(C.Structure):
     """rec_ids_group_plan_t (include/recengine.h)."""
     _fields_ = [("passes", C.c_int32), ("bits", C.c_int32 * 8), ("waves", C.c_int32), ("key_bytes", C.c_int32),
@@ -341,6 +345,11 @@ SIGNATURES = {
     "rec_ait_bwd": (C.c_int, [_I64, _I32, _I32, _P, _I64, _P, _P, _I64, _P, _I64, _P]),
     "rec_aitm_head": (C.c_int, [C.POINTER(AitmHeadDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "rec_auc_histogram_wide": (C.c_int, [_I64, _P, _I64, _P, _I32, _P, _P, _P]),
+    "rec_mind_routing_fwd": (C.c_int, [_I64, _I32, _I32, _I32, _I32, _P, _I64, _P, _P, _P, _P, _P, _P]),
+    "rec_mind_routing_bwd": (C.c_int, [_I64, _I32, _I32, _I32, _P, _P, _P, _P, _I64, _P]),
+    "rec_mind_label_attn_fwd": (C.c_int, [_I64, _I32, _I32, _F, _P, _I64, _P, _I64, _P, _I64, _P, _P]),
+    "rec_mind_label_attn_bwd": (C.c_int, [_I64, _I32, _I32, _F, _P, _I64, _P, _I64, _P, _P, _I64, _P, _I64, _P, _I64, _P]),
+    "rec_mind_ssm_head": (C.c_int, [_I64, _I32, _I32, _P, _I64, _P, _I64, _P, _P, _I64, _P, _P, _P, _P, _P, _F, _P, _P, _P, _I64, _P, _I64, _P]),
     "rec_dense_fold_fwd": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P]),
     "rec_dense_fold_bwd": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _I32, _P]),
     "rec_dense_fold_fwd_full": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P]),

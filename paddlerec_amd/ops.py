@@ -2698,6 +2698,101 @@ def auc_histogram_wide(pred, label, stat_pos, stat_neg, num_thresholds=100000):
                                        _stream()), "rec_auc_histogram_wide")
 
 
+# ------------------------------------------------------------------ MIND: capsule routing, label-aware attention, sampled softmax
+def mind_routing_fwd(low, seq_len, routing_logits, iters):
+    """MIND's dynamic routing in one launch (rec_mind_routing_fwd).  low [B * T, H]: a float32 view with a row stride, row
+    b * T + t the mapped history item t of sample b; seq_len [B] int64; routing_logits [K, T] (or [1, K, T]) contiguous.
+    -> (W [B, K, T] the final coupling weights, Z [B, K, H] the capsules before squash, caps [B, K, H] = squash(Z))."""
+    _chk(routing_logits, torch.float32, "routing_logits")
+    K, T = routing_logits.shape[-2:]
+    if routing_logits.numel() != K * T or low.dim() != 2 or low.shape[0] % T:
+        raise RecError("mind_routing_fwd: low must be [B * %d, H] and routing_logits [K, T], got %s and %s"
+                       % (T, tuple(low.shape), tuple(routing_logits.shape)))
+    B, H = low.shape[0] // T, low.shape[1]
+    ld = _mtl_view(low, B * T, H, "low")
+    _chk(seq_len, torch.int64, "seq_len", (B,))
+    f32 = dict(dtype=torch.float32, device=low.device)
+    W, Z, caps = torch.empty(B, K, T, **f32), torch.empty(B, K, H, **f32), torch.empty(B, K, H, **f32)
+    check(lib().rec_mind_routing_fwd(B, T, K, H, int(iters), _p(low), ld, _p(seq_len), _p(routing_logits), _p(W), _p(Z),
+                                     _p(caps), _stream()), "rec_mind_routing_fwd")
+    return W, Z, caps
+
+
+def mind_routing_bwd(d_caps, Z, W, out=None):
+    """Backward of the routing's last product (rec_mind_routing_bwd): d_caps, Z [B, K, H] and W [B, K, T] contiguous ->
+    d_low [B * T, H] (a view with a row stride when given).  W is a constant of the backward."""
+    _chk(Z, torch.float32, "Z")
+    B, K, H = Z.shape
+    _chk(d_caps, torch.float32, "d_caps", (B, K, H))
+    _chk(W, torch.float32, "W")
+    T = W.shape[2]
+    if tuple(W.shape) != (B, K, T):
+        raise RecError("mind_routing_bwd: W must be [B, K, T], got %s" % (tuple(W.shape),))
+    if out is None:
+        out = torch.empty(B * T, H, dtype=torch.float32, device=Z.device)
+    check(lib().rec_mind_routing_bwd(B, T, K, H, _p(d_caps), _p(Z), _p(W), _p(out), _mtl_view(out, B * T, H, "d_low"),
+                                     _stream()), "rec_mind_routing_bwd")
+    return out
+
+
+def mind_label_attn_fwd(caps2, target, k_max, pow_p=1.0):
+    """MIND's label-aware attention (rec_mind_label_attn_fwd): caps2 [B * K, H] and target [B, H], float32 views with a row
+    stride.  attn = softmax_k(pow(<caps2_k, target>, pow_p)), user = sum_k attn_k caps2_k.  -> (user [B, H], attn [B, K])."""
+    K = int(k_max)
+    if caps2.dim() != 2 or caps2.shape[0] % max(K, 1):
+        raise RecError("mind_label_attn_fwd: caps2 must be [B * k_max, H], got %s with k_max %d" % (tuple(caps2.shape), K))
+    B, H = caps2.shape[0] // max(K, 1), caps2.shape[1]
+    f32 = dict(dtype=torch.float32, device=caps2.device)
+    user, attn = torch.empty(B, H, **f32), torch.empty(B, K, **f32)
+    check(lib().rec_mind_label_attn_fwd(B, K, H, float(pow_p), _p(caps2), _mtl_view(caps2, B * K, H, "caps2"), _p(target),
+                                        _mtl_view(target, B, H, "target"), _p(user), 0, _p(attn), _stream()),
+          "rec_mind_label_attn_fwd")
+    return user, attn
+
+
+def mind_label_attn_bwd(caps2, target, attn, d_user, pow_p=1.0, d_target=None):
+    """Backward of mind_label_attn_fwd (rec_mind_label_attn_bwd): d_user [B, H] -> (d_caps2 [B * K, H], d_target [B, H]: a
+    view with a row stride when given)."""
+    _chk(attn, torch.float32, "attn")
+    B, K = attn.shape
+    H = caps2.shape[1]
+    f32 = dict(dtype=torch.float32, device=caps2.device)
+    d_caps2 = torch.empty(B * K, H, **f32)
+    if d_target is None:
+        d_target = torch.empty(B, H, **f32)
+    check(lib().rec_mind_label_attn_bwd(B, K, H, float(pow_p), _p(caps2), _mtl_view(caps2, B * K, H, "caps2"), _p(target),
+                                        _mtl_view(target, B, H, "target"), _p(attn), _p(d_user),
+                                        _mtl_view(d_user, B, H, "d_user"), _p(d_caps2), 0, _p(d_target),
+                                        _mtl_view(d_target, B, H, "d_target"), _stream()),
+          "rec_mind_label_attn_bwd")
+    return d_caps2, d_target
+
+
+def mind_ssm_head(user, true_w, true_b, S, sample_b, labels, neg, logq_true, logq_neg, grad_scale=1.0, d_true_w=None,
+                  d_user0=None):
+    """MIND's sampled-softmax head in one launch (rec_mind_ssm_head).  user, true_w [B, H] and S [B, n] (= user x sample_w^T)
+    float32 views with a row stride; true_b, logq_true [B], sample_b, logq_neg [n] float32 and labels [B], neg [n] int64
+    contiguous.  S is OVERWRITTEN with d(sample logits) = grad_scale * softmax (exactly 0 where labels[b] == neg[j]).
+    d_true_w, d_user0: [B, H] views with a row stride (or None) that receive d_true * user and d_true * true_w.
+    -> (loss [B] = -log_softmax of the true column, d_true [B], S)."""
+    B, H = user.shape
+    n = S.shape[1]
+    ldu, ldt, lds = _mtl_view(user, B, H, "user"), _mtl_view(true_w, B, H, "true_w"), _mtl_view(S, B, n, "S")
+    for t, name, shape in ((true_b, "true_b", (B,)), (logq_true, "logq_true", (B,)), (sample_b, "sample_b", (n,)),
+                           (logq_neg, "logq_neg", (n,))):
+        _chk(t, torch.float32, name, shape)
+    _chk(labels, torch.int64, "labels", (B,))
+    _chk(neg, torch.int64, "neg", (n,))
+    loss = torch.empty(B, dtype=torch.float32, device=user.device)
+    d_true = torch.empty(B, dtype=torch.float32, device=user.device)
+    check(lib().rec_mind_ssm_head(B, H, n, _p(user), ldu, _p(true_w), ldt, _p(true_b), _p(S), lds, _p(sample_b), _p(labels),
+                                  _p(neg), _p(logq_true), _p(logq_neg), float(grad_scale), _p(loss), _p(d_true), _p(d_true_w),
+                                  _mtl_view(d_true_w, B, H, "d_true_w") if d_true_w is not None else 0, _p(d_user0),
+                                  _mtl_view(d_user0, B, H, "d_user0") if d_user0 is not None else 0, _stream()),
+          "rec_mind_ssm_head")
+    return loss, d_true, S
+
+
 # ------------------------------------------------------------------ xDeepFM CIN (the passes around the GEMM)
 def _chk_f32(t, name):
     if not t.is_cuda:

@@ -711,3 +711,115 @@ class AitmReader:
                 a = torch.tensor(group, dtype=torch.int64)
                 group = []
                 yield tuple(t.contiguous().to(self.device, non_blocking=True) for t in (a[:, 2:], a[:, 0], a[:, 1]))
+
+
+class MindReader:
+    """models/recall/mind/mind_reader.py RecDataset with the batching of the other readers (drop_last).  Lines are
+    `user,item,timestamp`; a user's items are sorted by timestamp (a stable sort: ties keep file order).  An epoch draws
+    batch_size users at a time with random.sample until batches_per_epoch * batch_size samples have been yielded; a user
+    with at most 4 items is skipped; the cut position k is random.choice(range(4, len)) after random.seed(12345) — the
+    reference reseeds before EVERY choice, so k depends only on the history's length, and so does the stream that the next
+    random.sample continues from.  The history is the maxlen items before k (fewer: padded with 0 behind them).  Yields
+    (hist_item [B, maxlen] i64, target_item [B, 1] i64, seq_len [B, 1] i64) on `device`."""
+
+    def __init__(self, file_list, batch_size, device="cuda", maxlen=30, batches_per_epoch=1000):
+        self.file_list, self.batch_size, self.device = list(file_list), int(batch_size), device
+        self.maxlen, self.batches_per_epoch = int(maxlen), int(batches_per_epoch)
+        self.count = 0
+        self.graph, users, items = {}, set(), set()
+        for path in self.file_list:
+            with open(path, "r") as f:
+                for line in f:
+                    conts = line.strip().split(",")
+                    user_id, item_id, time_stamp = int(conts[0]), int(conts[1]), int(conts[2])
+                    users.add(user_id)
+                    items.add(item_id)
+                    self.graph.setdefault(user_id, []).append((item_id, time_stamp))
+        for user_id, value in self.graph.items():
+            value.sort(key=lambda x: x[1])
+            self.graph[user_id] = [x[0] for x in value]
+        self.users, self.items = list(users), list(items)
+
+    def samples(self):
+        """The reference's __iter__: one (hist_item [maxlen], target_item [1], seq_len [1]) int64 triple per sample."""
+        import random
+        random.seed(12345)
+        while True:
+            user_id_list = random.sample(self.users, self.batch_size)
+            if self.count >= self.batches_per_epoch * self.batch_size:
+                self.count = 0
+                break
+            for user_id in user_id_list:
+                item_list = self.graph[user_id]
+                if len(item_list) <= 4:
+                    continue
+                random.seed(12345)
+                k = random.choice(range(4, len(item_list)))
+                item_id = item_list[k]
+                if k >= self.maxlen:
+                    hist_item_list = item_list[k - self.maxlen:k]
+                    hist_item_len = len(hist_item_list)
+                else:
+                    hist_item_list = item_list[:k] + [0] * (self.maxlen - k)
+                    hist_item_len = k
+                self.count += 1
+                yield [np.array(hist_item_list).astype("int64"), np.array([item_id]).astype("int64"),
+                       np.array([hist_item_len]).astype("int64")]
+
+    def __iter__(self):
+        group = []
+        for s in self.samples():
+            group.append(s)
+            if len(group) == self.batch_size:
+                cols = [torch.from_numpy(np.stack([g[i] for g in group])) for i in range(3)]
+                group = []
+                yield tuple(t.contiguous().to(self.device, non_blocking=True) for t in cols)
+
+
+class MindInferReader:
+    """models/recall/mind/mind_infer_reader.py RecDataset with the batching of the other readers (drop_last).  Lines are
+    space-separated `slot:feasign` pairs of the slots hist_item and eval_item.  The history keeps its LAST maxlen items, the
+    evaluation list its FIRST maxlen, both padded with 0 behind; a line without an eval_item is skipped.  Yields
+    (hist_item [B, maxlen] i64, seq_len [B, 1] i64, eval_items [B, 1, maxlen] i64): the first two on `device`, the last on
+    the host, where the retrieval metrics are counted."""
+
+    def __init__(self, file_list, batch_size, device="cuda", maxlen=30):
+        self.file_list, self.batch_size, self.device, self.maxlen = list(file_list), int(batch_size), device, int(maxlen)
+        self.slots = "hist_item eval_item".split(" ")
+        self.padding = 0
+
+    def samples(self):
+        """The reference's __iter__: [hist_item [maxlen], seq_len [1], eval_items [1, maxlen]] int64 per line."""
+        slot2index = {s: i for i, s in enumerate(self.slots)}
+        for path in self.file_list:
+            with open(path, "r") as rf:
+                for line in rf:
+                    output = [(i, []) for i in self.slots]
+                    for i in line.strip().split(" "):
+                        slot_feasign = i.split(":")
+                        if slot_feasign[0] not in self.slots:
+                            continue
+                        output[slot2index[slot_feasign[0]]][1].append(int(slot_feasign[1]))
+                    output_list, seq_lens, eval_list = [], [], []
+                    for key, value in output:
+                        if key == "hist_item":
+                            seq_lens.append(min(self.maxlen, len(value)))
+                            value = value[-self.maxlen:] + [self.padding] * max(0, self.maxlen - len(value))
+                        if key == "eval_item":
+                            value = value[:self.maxlen] + [self.padding] * max(0, self.maxlen - len(value))
+                            eval_list.append(value)
+                            continue
+                        output_list.append(np.array(value).astype("int64"))
+                    if len(eval_list) == 0:
+                        continue
+                    yield output_list + [np.array(seq_lens).astype("int64")] + [np.array(eval_list).astype("int64")]
+
+    def __iter__(self):
+        group = []
+        for s in self.samples():
+            group.append(s)
+            if len(group) == self.batch_size:
+                cols = [torch.from_numpy(np.stack([g[i] for g in group])) for i in range(3)]
+                group = []
+                yield (cols[0].contiguous().to(self.device, non_blocking=True),
+                       cols[1].contiguous().to(self.device, non_blocking=True), cols[2])

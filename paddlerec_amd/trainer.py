@@ -10,7 +10,7 @@ What differs by construction: a batch never becomes 28 per-sample NumPy arrays (
 [B,26] / [B,13] device tensors), `loss.backward(); optimizer.step()` is the explicit `train_step` chain of the
 host mirrors, and the AUC buckets stay on the device (read back only when a log line prints them).
 
-    python -m paddlerec_amd.trainer -m <config.yaml> [--model deepfm|fm|ffm|deepfefm|fat_deepffm|wide_deep|dnn|dcn|dcn_v2|gatenet|flen|autofis|din|dien|dmr|bst|xdeepfm|dlrm|mmoe|ple|esmm|escm2|aitm] [-o runner.epochs=1 ...] [--infer]
+    python -m paddlerec_amd.trainer -m <config.yaml> [--model deepfm|fm|ffm|deepfefm|fat_deepffm|wide_deep|dnn|dcn|dcn_v2|gatenet|flen|autofis|din|dien|dmr|bst|xdeepfm|dlrm|mmoe|ple|esmm|escm2|aitm|mind] [-o runner.epochs=1 ...] [--infer]
     python -m torch.distributed.run --nproc-per-node G -m paddlerec_amd.trainer -m <config.yaml>     # collective mode
 """
 import argparse
@@ -25,7 +25,7 @@ from . import checkpoint
 logger = logging.getLogger("paddlerec_amd.trainer")
 
 MODELS = ("deepfm", "fm", "ffm", "deepfefm", "fat_deepffm", "wide_deep", "dnn", "dcn", "dcn_v2", "gatenet", "flen", "autofis",
-          "din", "dien", "dmr", "bst", "xdeepfm", "dlrm", "mmoe", "ple", "esmm", "escm2", "aitm")
+          "din", "dien", "dmr", "bst", "xdeepfm", "dlrm", "mmoe", "ple", "esmm", "escm2", "aitm", "mind")
 
 
 # ------------------------------------------------------------------------------------ configuration
@@ -118,6 +118,8 @@ def _dygraph_model(name):
         from .escm2 import DygraphModel
     elif name == "aitm":
         from .aitm import DygraphModel
+    elif name == "mind":
+        from .mind import DygraphModel
     else:
         raise ValueError("unknown model %r (known: %s)" % (name, ", ".join(MODELS)))
     return DygraphModel()
@@ -158,6 +160,12 @@ def create_data_loader(config, model, device, mode="train", shard=None):
         return lambda: iter(reader.AliCCPReader(files, bs, device, max_len=config.get("hyper_parameters.max_len", 3)))
     if model == "aitm":
         return lambda: iter(reader.AitmReader(files, bs, device))
+    if model == "mind":
+        maxlen = config.get("hyper_parameters.maxlen", 30)
+        if mode != "train":
+            return lambda: iter(reader.MindInferReader(files, bs, device, maxlen))
+        rd = reader.MindReader(files, bs, device, maxlen, config.get("runner.batches_per_epoch", 1000))
+        return lambda: iter(rd)                       # ONE reader: the user graph is built once
     if model == "flen":
         return lambda: iter(reader.AvazuReader(files, bs, device, shard=shard))
     if model == "autofis":
@@ -323,7 +331,7 @@ def _apply_optimizer_config(config, model, dy_model):
         logger.info("bst, kept as the reference writes it: %s; preprocess_cmd=%r postprocess_cmd=%r, Dropout(%.2f) with "
                     "the engine's counter-based masks (seed %d)", QUIRKS, dy_model.preprocess_cmd, dy_model.postprocess_cmd,
                     dy_model.dropout_rate, dy_model.dropout_seed)
-    if model in ("mmoe", "ple", "esmm", "escm2", "aitm"):
+    if model in ("mmoe", "ple", "esmm", "escm2", "aitm", "mind"):
         import importlib
         logger.info("%s, kept as the reference writes it: %s", model, importlib.import_module("." + model, __package__).QUIRKS)
         if model == "ple":
@@ -479,6 +487,8 @@ def infer(config, model, device="cuda", kernels=None, comm=None):
             raise ValueError("test_dataloader is null, please ensure batch size < dataset size!")
         _check_status(dy_model, comm, "infer")
         vals = _global_metric_values(dy_model_class, metric_list, metric_names, comm)
+        if hasattr(dy_model_class, "infer_summary"):      # metrics counted on the host beside the loop (mind: retrieval)
+            vals.update(dy_model_class.infer_summary())
         if use_auc:
             _reset(metric_list)
         logger.info("epoch: %d done, %s", epoch_id, "".join("%s: %.6f," % kv for kv in vals.items()))
