@@ -1591,6 +1591,10 @@ def record_gather(rows, rec, D, out_w, out_w1, status, table=None):
     if rec.dim() != 2 or rec.dtype != torch.float32 or not rec.is_cuda or rec.stride(1) != 1:
         raise RecError("rec must be a 2-D float32 device tensor with unit column stride")
     n = rows.numel()
+    _chk(out_w, torch.float32, "out_w")               # the kernel writes row i at out_w + i * D and out_w1[i]: no strides
+    _chk(out_w1, torch.float32, "out_w1")
+    if out_w.numel() != n * int(D) or out_w1.numel() != n:
+        raise RecError("record_gather: out_w must hold [n, D] and out_w1 [n] floats (n %d, D %d)" % (n, int(D)))
     lz = None
     if table is not None and not table.accessor.embed_zero_init and table.accessor.initial_range > 0:
         a = table.accessor      # embed_w (W1) of a key that does not exist yet reads as its creation value
@@ -2213,6 +2217,8 @@ def dmr_tail_fwd(hist, item_eb, uv, match_mask, V, cate_id, hist_sum, prod, rel_
     if D % 2 or V.shape[1] != D // 2 or any(tuple(t.shape) != (B, D) for t in (item_eb, hist_sum, prod)) or \
             tuple(rel_u2i.shape) != (B, 1) or tuple(match_mask.shape) != (B, 1):
         raise RecError("dmr_tail_fwd: shapes do not fit hist [B, T, 2E]")
+    if hist.stride(2) != 1 or (B > 1 and hist.stride(0) != T * hist.stride(1)):     # the kernel walks sample b at b * T * ldh
+        raise RecError("dmr_tail_fwd: hist must be [B, T, D] with one row stride")
     U2 = torch.empty(B, D // 2, dtype=torch.float32, device=hist.device)
     check(lib().rec_dmr_tail_fwd(B, T, D, _p(hist), hist.stride(1), _p(item_eb), _view_ld(item_eb), _p(uv), _p(match_mask),
                                  _view_ld(match_mask), _p(V), ldv, V.shape[0], _p(cate_id), _p(hist_sum), _view_ld(hist_sum), _p(prod),
@@ -2232,6 +2238,8 @@ def dmr_tail_bwd_match(dU2, d_rel, uv, match_mask, V, cate_id, dV_rows):
     _dev(match_mask, torch.int64, "match_mask")
     if tuple(d_rel.shape) != (B, 1) or tuple(dV_rows.shape) != (B, E) or tuple(match_mask.shape) != (B, 1):
         raise RecError("dmr_tail_bwd_match: d_rel / match_mask must be [B, 1] and dV_rows [B, E]")
+    if uv.shape[1] != 2 or V.dim() != 2 or V.shape[1] != E:           # the kernel reads E floats of a row of V per sample
+        raise RecError("dmr_tail_bwd_match: uv must be [B, 2, E] and V [C, E]")
     d_uv = torch.empty(B, 2, E, dtype=torch.float32, device=uv.device)
     check(lib().rec_dmr_tail_bwd_match(B, E, _p(dU2), _p(d_rel), _view_ld(d_rel), _p(uv), _p(match_mask), _view_ld(match_mask), _p(V),
                                        _chk_mat(V, "V"), V.shape[0], _p(cate_id), _p(d_uv), _p(dV_rows), _view_ld(dV_rows),
@@ -3041,6 +3049,8 @@ def sparse_adam_record_small(ids, slot_offset, padding_idx, grad, grad1, grad1_d
 def sgd_dense(p, g, lr):
     _chk(p, torch.float32, "p")
     _chk(g, torch.float32, "g")
+    if g.numel() != p.numel():
+        raise RecError("sgd_dense: %d gradients for %d parameters" % (g.numel(), p.numel()))
     check(lib().rec_sgd_dense(p.numel(), _p(p), _p(g), float(lr), _stream()), "rec_sgd_dense")
 
 
@@ -3049,6 +3059,8 @@ def bce_with_logits(logit, label, ws, mean_over=0):
     B = logit.numel()
     _chk(logit, torch.float32, "logit")
     _chk(label, torch.float32, "label")
+    if label.numel() != B:
+        raise RecError("bce_with_logits: %d labels for %d logits" % (label.numel(), B))
     dev = logit.device
     pred = torch.empty(B, 1, dtype=torch.float32, device=dev)
     dz = torch.empty(B, 1, dtype=torch.float32, device=dev)
