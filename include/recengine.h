@@ -2092,6 +2092,62 @@ int rec_mind_ssm_head(int64_t batch, int32_t hidden, int32_t n_sample, const flo
                       const int64_t* neg, const float* logq_true, const float* logq_neg, float grad_scale, float* loss,
                       float* d_true, float* d_true_w, int64_t ld_dtw, float* d_user0, int64_t ld_du0, void* stream);
 
+/* ----------------------------------------------------------------------------------------
+ * word2vec (models/recall/word2vec), skip-gram with negative sampling (csrc/w2v_ops.hip).  float32; no entry point takes a
+ * workspace; no float atomics; every sum has a fixed order, so a rerun is bit-identical.  Arguments are checked on the host
+ * before any launch (REC_EINVAL, the entry and the argument named in rec_last_error()); batch == 0 returns REC_OK without a
+ * launch after those checks.  A row stride ld_* of 0 means packed; a value below the packed width is refused; floats behind
+ * a row's width are never written.  Rows move as 16-byte vectors when emb_dim and the strides are multiples of 4 and the
+ * bases 16-byte aligned, float by float otherwise.  There is no padding id: id 0 is an ordinary word.
+ *
+ * rec_w2v_sgns_fwd_bwd: net.py:57-81 and dygraph_model.py:53-69.  in_ids int64 [batch]; target_ids int64 [batch, 1 + neg],
+ *   the true word first; emb, emb_w [num_rows, emb_dim] (ld_emb, ld_w), emb_b [num_rows, 1] (ld_b).
+ *     logit[b, j] = <emb[in_ids[b]], emb_w[target_ids[b, j]]> + emb_b[target_ids[b, j]]
+ *     p = 1 / (1 + exp(-logit));  term = -max(log(j == 0 ? p : 1 - p), -100)       (sigmoid, THEN BCE on the probability)
+ *     loss[0] = sum_b term[b, 0] / batch + sum_{b, j > 0} term[b, j] / (batch neg)   (each BCE takes its own mean)
+ *     g[b, j] = (p - y) / max((1 - p) p, 1e-12) * s_j * (1 - p) * p,  y = (j == 0),  s_0 = grad_scale / batch,
+ *               s_j = grad_scale / (batch neg): a saturated float32 sigmoid gives a term of 100 and g exactly 0
+ *     d_in[b] = sum_j g[b, j] emb_w[target_ids[b, j]]   ([batch, emb_dim], ld_din), j ascending
+ *   Outputs, packed: true_logits [batch], neg_logits [batch, neg], g [batch, 1 + neg], loss [1].  An id outside
+ *   [0, num_rows) sets REC_FLAG_INDEX_OOB in *status (may be NULL) and is never read: every pair (b, j) it takes part in has
+ *   logit 0, g 0 and no loss term (an input id: the whole sample and a zero d_in row).  emb_dim 1..REC_W2V_MAX_DIM,
+ *   neg 1..REC_W2V_MAX_NEG.
+ *
+ * rec_w2v_target_update: the SGD step of emb_w and emb_b.  n_uniq, uniq_rows, seg_offset, sorted_pos: the grouping of
+ *   target_ids viewed as [batch (1 + neg)] as rec_ids_group leaves it (its own workspace query is that entry's); g and
+ *   in_ids as above; emb is the input table BEFORE its own update and is only read.  For the u-th unique row r with the
+ *   occurrences pos_k (ascending):
+ *     dw = sum_k g[pos_k] emb[in_ids[pos_k / (1 + neg)]];  db = sum_k g[pos_k];  emb_w[r] -= lr dw;  emb_b[r] -= lr db
+ *   The [batch, 1 + neg, emb_dim] gradient is never written.  d_w_rows [n, emb_dim] (ld_dw) and d_b_rows [n], each may be
+ *   NULL, receive dw and db of unique row u.  A segment of at most 16 occurrences is summed in ascending order; a longer one
+ *   as 64 interleaved partials (occurrence i in partial i % 64, each ascending) folded in a fixed order.  An occurrence whose
+ *   input id is outside the table contributes nothing.  emb may not overlap emb_w (REC_EINVAL).
+ *
+ * rec_w2v_analogy_topk: net.py:100-110.  a, b, c int64 [n_query]; W [num_rows, emb_dim] (row_stride):
+ *     score[q, v] = <W[b_q] - W[a_q] + W[c_q], W[v]> / max(|W[v]|, 1e-12)
+ *   values [n_query, k] descending and ids int64 [n_query, k]; equal scores order by the lower id; an all-zero row scores
+ *   exactly 0.  The [n_query, num_rows] scores are never written: a block takes REC_W2V_TOPK_TILE_ROWS rows for all queries
+ *   and writes its k candidates per query to cand_values / cand_ids [n_tiles, n_query, k] (float32 / int64, the caller's),
+ *   a second kernel merges them; n_tiles must equal ceil(num_rows / REC_W2V_TOPK_TILE_ROWS).  k 1..REC_W2V_MAX_TOPK,
+ *   num_rows >= k.  An a / b / c outside the table sets REC_FLAG_INDEX_OOB in *status (may be NULL) and counts as a zero row.
+ * ---------------------------------------------------------------------------------------- */
+#define REC_W2V_MAX_DIM 1024
+#define REC_W2V_MAX_NEG 32
+#define REC_W2V_MAX_TOPK 8
+#define REC_W2V_TOPK_TILE_ROWS 128
+
+int rec_w2v_sgns_fwd_bwd(int64_t batch, int32_t emb_dim, int32_t neg, int64_t num_rows, const int64_t* in_ids,
+                         const int64_t* target_ids, const float* emb, int64_t ld_emb, const float* emb_w, int64_t ld_w,
+                         const float* emb_b, int64_t ld_b, float grad_scale, float* true_logits, float* neg_logits, float* g,
+                         float* d_in, int64_t ld_din, float* loss, int32_t* status, void* stream);
+int rec_w2v_target_update(int64_t batch, int32_t emb_dim, int32_t neg, int64_t num_rows, const int32_t* n_uniq,
+                          const int64_t* uniq_rows, const int32_t* seg_offset, const int32_t* sorted_pos, const float* g,
+                          const int64_t* in_ids, const float* emb, int64_t ld_emb, float* emb_w, int64_t ld_w, float* emb_b,
+                          int64_t ld_b, float lr, float* d_w_rows, int64_t ld_dw, float* d_b_rows, void* stream);
+int rec_w2v_analogy_topk(int64_t n_query, int32_t emb_dim, int64_t row_stride, int64_t num_rows, int32_t k, const int64_t* a,
+                         const int64_t* b, const int64_t* c, const float* W, float* cand_values, int64_t* cand_ids,
+                         int64_t n_tiles, float* values, int64_t* ids, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -222,6 +222,7 @@ class AitmHeadDesc(C.Structure):
 
 REC_MIND_MAX_T, REC_MIND_MAX_K, REC_MIND_MAX_H, REC_MIND_MAX_ITERS = 64, 8, 128, 8
 REC_MIND_HEAD_MAX_DIM, REC_MIND_MAX_NEG = 1024, 65536
+REC_W2V_MAX_DIM, REC_W2V_MAX_NEG, REC_W2V_MAX_TOPK, REC_W2V_TOPK_TILE_ROWS = 1024, 32, 8, 128
 
 
 class IdsGroupPlan(C.Structure):
@@ -350,6 +351,9 @@ SIGNATURES = {
     "rec_mind_label_attn_fwd": (C.c_int, [_I64, _I32, _I32, _F, _P, _I64, _P, _I64, _P, _I64, _P, _P]),
     "rec_mind_label_attn_bwd": (C.c_int, [_I64, _I32, _I32, _F, _P, _I64, _P, _I64, _P, _P, _I64, _P, _I64, _P, _I64, _P]),
     "rec_mind_ssm_head": (C.c_int, [_I64, _I32, _I32, _P, _I64, _P, _I64, _P, _P, _I64, _P, _P, _P, _P, _P, _F, _P, _P, _P, _I64, _P, _I64, _P]),
+    "rec_w2v_sgns_fwd_bwd": (C.c_int, [_I64, _I32, _I32, _I64, _P, _P, _P, _I64, _P, _I64, _P, _I64, _F, _P, _P, _P, _P, _I64, _P, _P, _P]),
+    "rec_w2v_target_update": (C.c_int, [_I64, _I32, _I32, _I64, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _F, _P, _I64, _P, _P]),
+    "rec_w2v_analogy_topk": (C.c_int, [_I64, _I32, _I64, _I64, _I32, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P]),
     "rec_dense_fold_fwd": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P]),
     "rec_dense_fold_bwd": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _I32, _P]),
     "rec_dense_fold_fwd_full": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _P]),

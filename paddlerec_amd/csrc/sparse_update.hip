@@ -2098,7 +2098,9 @@ extern "C" int rec_sparse_sgd_rows(int64_t n_max, int32_t emb_dim, int32_t row_s
   if (n_max == 0) return REC_OK;
   const bool gvec = ((uintptr_t)grad) % 16 == 0 && (gl.group <= 0 || gl.group_stride % 4 == 0) &&
                     ((uintptr_t)P) % 16 == 0;
-  return dispatch_row_shape(emb_dim, gvec ? row_stride : row_stride | 1, [&](auto vec, auto lanes) -> int {
+  // float4 rows of 257..1024 floats (word2vec's 300) take LANES 128 / 256: the kernel gives a row LANES THREADS, which a
+  // block of kBlock holds whole, so unlike the wave-per-row kernels it needs no column passes
+  return dispatch_row_shape_wide(emb_dim, gvec ? row_stride : row_stride | 1, [&](auto vec, auto lanes) -> int {
     constexpr int VEC = decltype(vec)::value, LANES = decltype(lanes)::value;
     const int64_t grid = (n_max * LANES + kBlock - 1) / kBlock;
     REC_REQUIRE(grid < (1ll << 31), REC_ESHAPE, "too many rows");

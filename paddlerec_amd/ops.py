@@ -2801,6 +2801,92 @@ def mind_ssm_head(user, true_w, true_b, S, sample_b, labels, neg, logq_true, log
     return loss, d_true, S
 
 
+# ------------------------------------------------------------------ word2vec: skip-gram with negative sampling
+def _w2v_tables(emb, emb_w, emb_b, what):
+    """The three tables of Word2VecLayer -> (V, D, ld_emb, ld_w, ld_b); emb_b is [V, 1] (or [V])."""
+    D, ld_e = _chk_table(emb, "emb")
+    Dw, ld_w = _chk_table(emb_w, "emb_w")
+    Db, ld_b = _chk_table(emb_b, "emb_b")
+    V = emb.shape[0]
+    if emb.dim() != 2 or tuple(emb_w.shape) != (V, D) or emb_b.shape[0] != V or Db != 1:
+        raise RecError("%s: expected emb, emb_w [V, D] and emb_b [V, 1], got %s, %s, %s"
+                       % (what, tuple(emb.shape), tuple(emb_w.shape), tuple(emb_b.shape)))
+    return V, D, ld_e, ld_w, ld_b
+
+
+def w2v_sgns_fwd_bwd(in_ids, target_ids, emb, emb_w, emb_b, grad_scale=1.0, status=None, d_in=None):
+    """Skip-gram with negative sampling, forward and the gradient of the logits in one launch (rec_w2v_sgns_fwd_bwd).
+    in_ids [B] and target_ids [B, 1 + neg] (the true word first) int64 contiguous; emb, emb_w [V, D] and emb_b [V, 1] float32
+    tables with a row stride.  d_in: a [B, D] view with a row stride (or None).
+    -> (true_logits [B], neg_logits [B, neg], g [B, 1 + neg] = d loss / d logit, d_in [B, D], loss [1], status)."""
+    V, D, ld_e, ld_w, ld_b = _w2v_tables(emb, emb_w, emb_b, "w2v_sgns_fwd_bwd")
+    _chk(in_ids, torch.int64, "in_ids")
+    B = in_ids.numel()
+    _chk(target_ids, torch.int64, "target_ids")
+    if in_ids.dim() != 1 or target_ids.dim() != 2 or target_ids.shape[0] != B or target_ids.shape[1] < 2:
+        raise RecError("w2v_sgns_fwd_bwd: expected in_ids [B] and target_ids [B, 1 + neg], got %s and %s"
+                       % (tuple(in_ids.shape), tuple(target_ids.shape)))
+    neg = target_ids.shape[1] - 1
+    dev = emb.device
+    if status is None:
+        status = new_status(dev)
+    f32 = dict(dtype=torch.float32, device=dev)
+    if d_in is None:
+        d_in = torch.empty(B, D, **f32)
+    true_logits, neg_logits, g = torch.empty(B, **f32), torch.empty(B, neg, **f32), torch.empty(B, 1 + neg, **f32)
+    loss = torch.zeros(1, **f32)
+    check(lib().rec_w2v_sgns_fwd_bwd(B, D, neg, V, _p(in_ids), _p(target_ids), _p(emb), ld_e, _p(emb_w), ld_w, _p(emb_b), ld_b,
+                                     float(grad_scale), _p(true_logits), _p(neg_logits), _p(g), _p(d_in),
+                                     _mtl_view(d_in, B, D, "d_in"), _p(loss), _p(status), _stream()), "rec_w2v_sgns_fwd_bwd")
+    return true_logits, neg_logits, g, d_in, loss, status
+
+
+def w2v_target_update(groups, g, in_ids, emb, emb_w, emb_b, lr, d_w_rows=None, d_b_rows=None):
+    """The SGD step of emb_w / emb_b from g and the PRE-update input table (rec_w2v_target_update): groups is
+    ids_group(target_ids.reshape(-1)); the merged gradient of unique row u goes to d_w_rows [n, D] / d_b_rows [n] when given.
+    The [B, 1 + neg, D] gradient is never written.  emb may not overlap emb_w."""
+    V, D, ld_e, ld_w, ld_b = _w2v_tables(emb, emb_w, emb_b, "w2v_target_update")
+    _chk(g, torch.float32, "g")
+    _chk(in_ids, torch.int64, "in_ids")
+    B = in_ids.numel()
+    if g.dim() != 2 or g.shape[0] != B or g.numel() != groups.n:
+        raise RecError("w2v_target_update: g %s does not match in_ids [%d] and a grouping of %d ids" % (tuple(g.shape), B, groups.n))
+    neg = g.shape[1] - 1
+    ld_dw = 0
+    if d_w_rows is not None:
+        ld_dw = _mtl_view(d_w_rows, groups.n, D, "d_w_rows")
+    _chk(d_b_rows, torch.float32, "d_b_rows", (groups.n,))
+    check(lib().rec_w2v_target_update(B, D, neg, V, _p(groups.n_uniq), _p(groups.uniq_rows), _p(groups.seg_offset),
+                                      _p(groups.sorted_pos), _p(g), _p(in_ids), _p(emb), ld_e, _p(emb_w), ld_w, _p(emb_b), ld_b,
+                                      float(lr), _p(d_w_rows), ld_dw, _p(d_b_rows), _stream()), "rec_w2v_target_update")
+
+
+def w2v_analogy_topk(a, b, c, W, k=4, status=None, cand=None):
+    """The analogy search of Word2VecInferLayer without the [Q, V] scores (rec_w2v_analogy_topk): a, b, c int64 [Q]; W [V, D]
+    with a row stride; score = <W[b] - W[a] + W[c], W[v]> / max(|W[v]|, 1e-12).  cand: (values, ids) candidate buffers
+    [tiles, Q, k] float32 / int64 to reuse (allocated when None or of another shape).
+    -> (values [Q, k] descending, ids [Q, k] int64; equal scores by the lower id)."""
+    D, ld = _chk_table(W, "W")
+    if W.dim() != 2:
+        raise RecError("w2v_analogy_topk: W must be [V, D]")
+    V, k = W.shape[0], int(k)
+    Q = a.numel()
+    for t, name in ((a, "a"), (b, "b"), (c, "c")):
+        _chk(t, torch.int64, name, (Q,))
+    tiles = (V + _lib.REC_W2V_TOPK_TILE_ROWS - 1) // _lib.REC_W2V_TOPK_TILE_ROWS
+    dev = W.device
+    if cand is None or tuple(cand[0].shape) != (tiles, Q, k) or tuple(cand[1].shape) != (tiles, Q, k):
+        cand = (torch.empty(tiles, Q, max(k, 0), dtype=torch.float32, device=dev),
+                torch.empty(tiles, Q, max(k, 0), dtype=torch.int64, device=dev))
+    _chk(cand[0], torch.float32, "cand values")
+    _chk(cand[1], torch.int64, "cand ids")
+    values = torch.empty(Q, max(k, 0), dtype=torch.float32, device=dev)
+    ids = torch.empty(Q, max(k, 0), dtype=torch.int64, device=dev)
+    check(lib().rec_w2v_analogy_topk(Q, D, ld, V, k, _p(a), _p(b), _p(c), _p(W), _p(cand[0]), _p(cand[1]), tiles, _p(values),
+                                     _p(ids), _p(status), _stream()), "rec_w2v_analogy_topk")
+    return values, ids
+
+
 # ------------------------------------------------------------------ xDeepFM CIN (the passes around the GEMM)
 def _chk_f32(t, name):
     if not t.is_cuda:

@@ -823,3 +823,88 @@ class MindInferReader:
                 group = []
                 yield (cols[0].contiguous().to(self.device, non_blocking=True),
                        cols[1].contiguous().to(self.device, non_blocking=True), cols[2])
+
+
+class Word2vecReader:
+    """models/recall/word2vec/word2vec_reader.py RecDataset (with_shuffle_batch False) with the batching of the other readers
+    (drop_last).  A line is a sentence of word ids; every word is paired with each word of its window.  The window is ONE
+    draw made at construction — np.random.seed(12345); np.random.randint(1, window_size + 1) (word2vec_reader.py:60-61): 3 for
+    window_size 5 — used for every word.  The negatives are cs.searchsorted of neg_num random.random() draws, cs the cumulative
+    0.75-power unigram distribution of word_count_dict_path's counts; random.seed(12345) runs before EVERY sample's draws
+    (word2vec_reader.py:113-116), so every sample gets the SAME neg_num ids.  Yields (in_ids [B] i64, target_ids [B, 1 + neg]
+    i64, the true word first) on `device`: one tensor, so the step has no concat."""
+
+    def __init__(self, file_list, batch_size, device="cuda", word_count_dict_path=None, window_size=5, neg_num=5):
+        self.file_list, self.batch_size, self.device = list(file_list), int(batch_size), device
+        self.window_size, self.neg_num = int(window_size), int(neg_num)
+        np.random.seed(12345)
+        self.window = int(np.random.randint(1, self.window_size + 1))
+        id_counts = []
+        with open(word_count_dict_path, "r", encoding="utf-8") as f:
+            for line in f:
+                id_counts.append(int(line.split()[1]))
+        word_all_count = sum(id_counts)
+        np_power = np.power(np.array([float(count) / word_all_count for count in id_counts]), 0.75)
+        self.cs = np.array(np_power / np_power.sum()).cumsum()
+
+    def negatives(self):
+        """The neg_num ids every sample gets."""
+        import random
+        random.seed(12345)
+        return self.cs.searchsorted([random.random() for _ in range(self.neg_num)]).astype("int64")
+
+    def samples(self):
+        """The reference's __iter__: (input word, true word, negatives [neg_num]) per (word, context word) pair."""
+        for path in self.file_list:
+            with open(path, "r") as rf:
+                for line in rf:
+                    words = line.split()
+                    for idx, target_id in enumerate(words):
+                        start = max(idx - self.window, 0)
+                        for context_id in words[start:idx] + words[idx + 1:idx + self.window + 1]:
+                            yield int(target_id), int(context_id), self.negatives()
+
+    def __iter__(self):
+        ins, tgt = [], []
+        for w, c, neg in self.samples():
+            ins.append(w)
+            tgt.append(np.concatenate([[c], neg]))
+            if len(ins) == self.batch_size:
+                a, b = torch.from_numpy(np.asarray(ins, np.int64)), torch.from_numpy(np.stack(tgt).astype(np.int64))
+                ins, tgt = [], []
+                yield a.to(self.device, non_blocking=True), b.contiguous().to(self.device, non_blocking=True)
+
+
+class Word2vecInferReader:
+    """models/recall/word2vec/word2vec_infer_reader.py RecDataset with drop_last batching.  A line is four words `a b c d`
+    (lower-cased; a word missing from word_id_dict_path becomes <UNK>); reading STOPS at the first line that holds a ':'
+    (word2vec_infer_reader.py:88-89).  Yields (a [B, 1], b [B, 1], c [B, 1], label [B, 1] i64 on `device`, inputs_word
+    [B, 3] i64 on the host, where the first-that-is-no-input rule runs)."""
+
+    def __init__(self, file_list, batch_size, device="cuda", word_id_dict_path=None):
+        self.file_list, self.batch_size, self.device = list(file_list), int(batch_size), device
+        self.word_to_id, self.id_to_word = {}, {}
+        with open(word_id_dict_path, "r", encoding="utf-8") as f:
+            for line in f:
+                self.word_to_id[line.split(" ")[0]] = int(line.split(" ")[1])
+                self.id_to_word[int(line.split(" ")[1])] = line.split(" ")[0]
+        self.dict_size = len(self.word_to_id)
+
+    def samples(self):
+        for path in self.file_list:
+            with open(path, "r") as rf:
+                for line in rf:
+                    if ":" in line:
+                        return
+                    features = [w if w in self.word_to_id else "<UNK>" for w in line.lower().split()]
+                    ids = [self.word_to_id[features[i]] for i in range(4)]
+                    yield [np.array([i]).astype("int64") for i in ids] + [np.array(ids[:3]).astype("int64")]
+
+    def __iter__(self):
+        group = []
+        for s in self.samples():
+            group.append(s)
+            if len(group) == self.batch_size:
+                cols = [torch.from_numpy(np.stack([g[i] for g in group])) for i in range(5)]
+                group = []
+                yield tuple(t.contiguous().to(self.device, non_blocking=True) for t in cols[:4]) + (cols[4],)
