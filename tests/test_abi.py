@@ -218,3 +218,101 @@ def test_cross_layer_workspace_covers_the_strides_of_the_call(engine_lib):
         rc = L.rec_crossnet_v2_layer_bwd(C.byref(_lib.CrossV2Desc(B, d, 0, 0, 0, 0)), p, p, p, p, p, 0, p, 0, 0, 1, q, wide,
                                          p, p, p, C.c_size_t(plain.value), None)
         assert rc == -3 and b"ld_out" in L.rec_last_error()
+
+
+# ------------------------------------------------------------------------------------------------ the parsed binding
+# paddlerec_amd/_lib.py derives constants, structs and signatures from include/recengine.h.  A comparison of the binding
+# with the header is therefore header against header; what follows pins the PARSER: against literals written out by
+# hand, against the host compiler's layout of every struct, and on text it has to refuse.
+def test_parsed_signatures_match_literals():
+    import ctypes as C
+    from paddlerec_amd import _lib
+    P, I64, I32, F, SZ = C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_size_t
+    S = _lib.SIGNATURES
+    assert S["rec_last_error"] == (C.c_char_p, [])
+    assert S["rec_ps_init_value_host"] == (C.c_float, [C.c_uint64, I64, I32, F])
+    assert S["rec_xxh32"] == (C.c_uint32, [P, SZ, C.c_uint32])
+    assert S["rec_gemm_f32"] == (C.c_int, [C.POINTER(_lib.GemmDesc), P, P, P, C.POINTER(_lib.GemmEpilogueArgs), P, SZ, P])
+    assert S["rec_w2v_sgns_fwd_bwd"] == (C.c_int, [I64, I32, I32, I64, P, P, P, I64, P, I64, P, I64, F, P, P, P, P, I64, P,
+                                                   P, P])
+    assert S["rec_bst_embed_fwd"] == (C.c_int, [I64, I32, P, P, P, P, P, P, I64, P, I64, P, P])       # T* const* is a pointer
+    assert S["rec_autofis_fwd"] == (C.c_int, [I64, I32, I32, I32, I32, I64, P, P, P, I32, P, P, P, P, P, P, P, P, F, F, I32,
+                                              I32, P, I64, P, I64, P, P, P, P, P, SZ, P])
+    assert len(S["rec_autofis_fwd"][1]) == 33 == max(len(a) for _, a in S.values())
+
+
+def test_parsed_structs_and_constants_match_literals():
+    import ctypes as C
+    from paddlerec_amd import _lib
+    P, I64, I32 = C.c_void_p, C.c_int64, C.c_int32
+    assert _lib.GemmDesc is _lib.STRUCTS["rec_gemm_desc"] and _lib.GemmDesc.__name__ == "GemmDesc"
+    assert _lib.GemmDesc._fields_ == [("m", I64)] + [(n, I32) for n in (
+        "n", "k", "lda", "ldb", "ldc", "trans_a", "trans_b", "epilogue", "split_k", "num_cus")]
+    assert _lib.SmallSgdJob._fields_ == [("n", I64), ("emb_dim", I32), ("row_stride", I32), ("num_rows", I64),
+                                         ("padding_idx", I64), ("ids", P), ("grad", P),
+                                         ("grad_layout", _lib.GradLayout), ("P", P)]              # nested by value
+    assert _lib.GradLayout._fields_ == [("div", I32), ("group", I32), ("group_stride", I64), ("partials", P),
+                                        ("index", P), ("sorted", I32)]
+    assert _lib.MtlMixDesc._fields_ == (
+        [("batch", I64), ("expert_size", I32), ("n_slots", I32), ("n_gates", I32)] +
+        [(n, I64) for n in ("ld_h", "ld_logit", "ld_prob", "ld_out", "ld_dh", "ld_dlogit")] +
+        [(n, I32 * 16) for n in ("first0", "count0", "first1", "count1")])                        # [REC_MTL_MAX_GATES]
+    assert _lib.REC_AUC_WIDE_MAX_THRESHOLDS == 16777216 and _lib.REC_EHIP == -4 and _lib.REC_GEMM_ROUTE_PAIR == 64
+    assert _lib.EPI == dict(none=0, bias=1, bias_relu=2, relu_mask=3, cross=4, bias_sigmoid=5, bias_tanh=6, add=7, moe=8,
+                            dsigmoid=9, dtanh=10)
+    assert len(_lib.STRUCTS) == 29 == len(_lib._STRUCT_NAMES) and set(_lib.STRUCTS) == set(_lib._STRUCT_NAMES)
+
+
+def test_struct_layouts_match_the_host_compiler(tmp_path):
+    """sizeof and every offsetof of all structs, as the C compiler lays out include/recengine.h."""
+    import ctypes as C
+    import shutil
+    import subprocess
+    import pytest
+    from paddlerec_amd import _lib
+    cc = shutil.which("cc") or shutil.which("gcc") or shutil.which("clang")
+    if cc is None:
+        pytest.skip("no host C compiler")
+    lines = ['#include <stdio.h>', '#include "recengine.h"', "int main(void) {"]
+    want = []
+    for cname, cls in sorted(_lib.STRUCTS.items()):
+        lines.append('  printf("%s %%zu\\n", sizeof(%s));' % (cname, cname))
+        want.append("%s %d" % (cname, C.sizeof(cls)))
+        for field, _ in cls._fields_:
+            lines.append('  printf("%s.%s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s*)0)->%s));'
+                         % (cname, field, cname, field, cname, field))
+            want.append("%s.%s %d %d" % (cname, field, getattr(cls, field).offset, getattr(cls, field).size))
+    src = tmp_path / "layout.c"
+    src.write_text("\n".join(lines + ["  return 0;", "}", ""]))
+    exe = str(tmp_path / "layout")
+    subprocess.check_call([cc, "-I", os.path.join(REPO, "include"), str(src), "-o", exe])
+    got = subprocess.check_output([exe]).decode().split("\n")
+    assert len(want) > 29 + 300 and got[:-1] == want
+
+
+def test_parser_refuses_what_it_does_not_recognise(monkeypatch):
+    import pytest
+    from paddlerec_amd import _lib
+    from paddlerec_amd._lib import RecError, parse_header
+    assert _lib.HEADER_PATH == os.path.join(REPO, "include", "recengine.h")
+    monkeypatch.setattr(_lib, "HEADER_PATH", os.path.join(REPO, "include", "no_such.h"))
+    with pytest.raises(RecError, match="no_such.h"):                                   # a missing header names the path tried
+        _lib._read_header()
+    ok = "typedef struct { int32_t a, *b; } rec_s;\nint rec_f(const rec_s* s, float x); /* rec_g( */\n"
+    consts, structs, sigs = parse_header("#define REC_N (1 << 3)\nenum { REC_A = REC_N + 1 };\n" + ok)
+    assert consts == dict(REC_N=8, REC_A=9) and list(structs) == ["rec_s"] and list(sigs) == ["rec_f"]
+    for bad, word in (("int rec_f(double x);", "double"),                               # unknown type in a prototype
+                      ("int rec_f(double* x);", "double"),                              # ... also behind a pointer
+                      ("typedef struct { long a; } rec_s;", "long"),
+                      ("typedef struct { int32_t a[REC_NOPE]; } rec_s;", "REC_NOPE"),
+                      ("typedef enum { REC_A = 0, REC_B } rec_e;", "REC_B"),            # valueless enumerator
+                      ("struct rec_fwd;", "struct rec_fwd"),                            # declarations it cannot place
+                      ("int rec_f(int32_t (*cb)(void));", "rec_f"),
+                      ("static int rec_x = 3;", "rec_x"),
+                      ("int rec_f(void)", "rec_f"),                                     # no terminating ';'
+                      ("int rec_f(void);\nint rec_f(void);", "rec_f"),
+                      ("#define REC_X 1.5", "REC_X"),
+                      ("#if 0\n#endif", "#if 0")):
+        with pytest.raises(RecError) as e:
+            parse_header(bad)
+        assert word in str(e.value), (bad, str(e.value))
