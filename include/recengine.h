@@ -2148,6 +2148,99 @@ int rec_w2v_analogy_topk(int64_t n_query, int32_t emb_dim, int64_t row_stride, i
                          const int64_t* b, const int64_t* c, const float* W, float* cand_values, int64_t* cand_ids,
                          int64_t n_tiles, float* values, int64_t* ids, int32_t* status, void* stream);
 
+/* ----------------------------------------------------------------------------------------
+ * TiSASRec (models/recall/tisas), time-interval-aware self-attention (csrc/tisas_ops.hip).  float32; no float atomics;
+ * every sum has a fixed order, so a rerun is bit-identical.  No entry point takes a workspace: what a call needs beyond its
+ * results are buffers of the caller's whose sizes follow from the shapes (gs, ga, partials below).  Arguments are checked
+ * on the host before any launch (REC_EINVAL, the entry named in rec_last_error()); a size of 0 rows returns REC_OK without
+ * a launch after those checks.  A mask stream is rec_dropout's: element e of the named virtual matrix is kept iff
+ * rec_dropout with the same (p, seed, stream id) keeps it, and a kept value is multiplied by 1 / (1 - p); with p = 0 no
+ * random number is drawn.
+ *
+ * rec_tisas_attn_fwd: net.py:85-164 after the three projections.  q, k, v [batch * seq_len, hidden] (ldq, ldk, ldv); heads
+ *   are contiguous column slices of head = hidden / n_head.  tables: a HOST array of 4 device pointers pos_k, pos_v
+ *   [seq_len, hidden] and time_k, time_v [time_rows, hidden], all packed.  tm int64 [batch, seq_len, seq_len]; log_seqs int64
+ *   [batch, seq_len].  probs: HOST float[3] = dropout on the attention weights, the position rows, the time rows; streams:
+ *   HOST uint64[5] = the mask streams of the weights (virtual [batch n_head seq_len, seq_len], as rec_mha_fwd), pos_k, pos_v
+ *   (virtual [batch seq_len, hidden]: per sample), time_k, time_v (virtual [batch seq_len seq_len, hidden]).
+ *     s_ij = scale q_i . (k_j + drop(pos_k)_bj + drop(time_k[tm[b,i,j]])_bij)          per head
+ *     s_ij = -2^32 + 1 for EVERY j when log_seqs[b,i] == 0, and for j > i (a replacement, not an addition): a padded query
+ *            row attends uniformly, 1 / seq_len, over all keys, future ones included
+ *     a_i = drop(softmax_j s_ij);  out_i = sum_j a_ij (v_j + drop(pos_v)_bj + drop(time_v[tm[b,i,j]])_bij), j ascending
+ *   out [batch * seq_len, hidden] (ldo), lse [batch, n_head, seq_len] = max_j s_ij + log sum_j exp(s_ij - max).  An id of tm
+ *   outside [0, time_rows) sets REC_FLAG_INDEX_OOB in *status (may be NULL) and reads row 0.  The [batch, seq_len, seq_len,
+ *   hidden] relation tensors are never formed: the time rows are gathered from the tables (L2-resident) per (i, j).
+ *   Limits: seq_len 1..REC_TISAS_MAX_L, head 1..REC_TISAS_MAX_HEAD, seq_len * (head | 1) <= REC_TISAS_MAX_TILE (one
+ *   sample's keys and values of a head sit in LDS), time_rows >= 1; anything else is REC_EINVAL.
+ *
+ * rec_tisas_attn_bwd: the same inputs, d_out [batch * seq_len, hidden] (ld_dout) and the forward's lse.  The weights are
+ *   recomputed from lse and renormalised by their own sum (lse of a padded row rounds to -2^32).  Writes dq, dk, dv
+ *   (lddq, lddk, lddv) and, through d_tables (HOST array of 4 device pointers, shapes of tables): d_pos_k, d_pos_v summed
+ *   over the batch in ascending sample order, and d_time_k, d_time_v: row t is the sum over every (b, i, j) with
+ *   tm[b,i,j] == t, a row nothing hit is exactly 0.  accumulate != 0 adds the four to what d_tables hold.  gs, ga
+ *   [batch * n_head * seq_len * seq_len] receive scale * d s_ij and the dropped weights a_ij (the two small score-shaped
+ *   arrays the key-side and table passes read);
+ *   partials holds min(batch, REC_TISAS_MAX_PARTIALS) * 2 * time_rows * hidden floats: block p sums the samples
+ *   b with b / ceil(batch / P) == p into its own [time_rows, head] LDS tile in ascending (b, i, j), one fold adds the
+ *   tiles in ascending p.  Additional limit: time_rows * head <= REC_TISAS_MAX_TIME_TILE.
+ *
+ * rec_affine_layer_norm_fwd: t = x + r (r may be NULL), t = 0 in the rows whose row_ids entry (int64 [m], may be NULL) is 0;
+ *   y = (t - mean) rstd gamma + beta over the last axis, biased variance, rstd = 1 / sqrt(var + eps).  sum_out (may be NULL;
+ *   may be x) receives t.  mean, rstd [m] are saved.  paddle.nn.LayerNorm(hidden, epsilon) with the residual add and the
+ *   `seqs *= (log_seqs != 0)` in front of it (net.py:273-287).
+ * rec_affine_layer_norm_bwd: t as the forward formed it; g = dy + dy2 (dy2 may be NULL).
+ *     dx = (rstd (g gamma - mean(g gamma) - xhat mean(g gamma xhat)) + e1 + e2), 0 in the rows row_ids masks
+ *   — the gradient of x and of r alike; e1, e2 (may be NULL) are further gradients of t.  dx may be dy.  dgamma[c] = sum_rows
+ *   g xhat, dbeta[c] = sum_rows g: one block per column, rows strided over its threads, then a tree (fixed order).
+ *
+ * rec_tisas_embed_fwd: out[r] = drop(table[ids[r]] * scale), a zero row for id 0 (padding_idx 0; net.py:245-247,263).  The
+ *   mask stream's virtual matrix is [n, dim].  An id outside [0, num_rows) sets REC_FLAG_INDEX_OOB and gives a zero row.
+ * rec_tisas_embed_bwd: rows[r] = the gradient of table[ids[r]]: d_out[r] * scale through the same mask, zero for id 0.
+ *
+ * rec_tisas_head: net.py:305-308 and dygraph_model.py:42-53.  feats [n, dim] (ld_feats), pos, neg int64 [n]:
+ *     pl = <feats_r, table[pos_r]>, nl = <feats_r, table[neg_r]>, selected = pos_r != 0, cnt = the selected count
+ *     loss2[0] = sum_selected (softplus(-pl) + softplus(nl)) / cnt, loss2[1] = cnt — taken on the device, no host sync;
+ *     cnt == 0 gives loss NaN, as the reference's mean over an empty selection, and zero gradients
+ *     coef_pos[r] = (sigmoid(pl) - 1) / cnt, coef_neg[r] = sigmoid(nl) / cnt, both 0 where not selected
+ *     d_feats[r] = coef_pos table[pos_r] + coef_neg table[neg_r];  d_pos_rows[r] = coef_pos feats_r, d_neg_rows[r] =
+ *     coef_neg feats_r (each [n, dim] with its row stride; either may be NULL).  row_loss [n] receives the per-row terms,
+ *     pos_logits, neg_logits [n] (either may be NULL) pl and nl.
+ *   An id outside [0, num_rows) sets REC_FLAG_INDEX_OOB and reads as a zero row.  dim 1..REC_TISAS_HEAD_MAX_DIM.
+ * ---------------------------------------------------------------------------------------- */
+#define REC_TISAS_MAX_L 128
+#define REC_TISAS_MAX_HEAD 64
+#define REC_TISAS_MAX_TILE 7168
+#define REC_TISAS_MAX_TIME_TILE 16384
+#define REC_TISAS_MAX_PARTIALS 128
+#define REC_TISAS_HEAD_MAX_DIM 1024
+
+int rec_tisas_attn_fwd(int64_t batch, int32_t seq_len, int32_t n_head, int32_t hidden, int32_t time_rows, const float* q,
+                       int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv, const float* const* tables,
+                       const int64_t* tm, const int64_t* log_seqs, float scale, const float* probs, uint64_t seed,
+                       const uint64_t* streams, float* out, int64_t ldo, float* lse, int32_t* status, void* stream);
+int rec_tisas_attn_bwd(int64_t batch, int32_t seq_len, int32_t n_head, int32_t hidden, int32_t time_rows, const float* q,
+                       int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv, const float* const* tables,
+                       const int64_t* tm, const int64_t* log_seqs, float scale, const float* probs, uint64_t seed,
+                       const uint64_t* streams, const float* d_out, int64_t ld_dout, const float* lse, float* gs, float* ga,
+                       float* dq, int64_t lddq, float* dk, int64_t lddk, float* dv, int64_t lddv, float* const* d_tables,
+                       float* partials, int32_t accumulate, void* stream);
+int rec_affine_layer_norm_fwd(int64_t m, int32_t n, const float* x, int64_t ldx, const float* r, int64_t ldr,
+                              const float* gamma, const float* beta, float eps, const int64_t* row_ids, float* sum_out,
+                              int64_t ld_sum, float* y, int64_t ldy, float* mean, float* rstd, void* stream);
+int rec_affine_layer_norm_bwd(int64_t m, int32_t n, const float* t, int64_t ldt, const float* mean, const float* rstd,
+                              const float* gamma, const float* dy, int64_t lddy, const float* dy2, int64_t lddy2,
+                              const float* e1, int64_t lde1, const float* e2, int64_t lde2, const int64_t* row_ids, float* dx,
+                              int64_t lddx, float* dgamma, float* dbeta, void* stream);
+int rec_tisas_embed_fwd(int64_t n, int32_t dim, int64_t num_rows, const int64_t* ids, const float* table, int64_t ld_table,
+                        float scale, float p, uint64_t seed, uint64_t stream_id, float* out, int64_t ldo, int32_t* status,
+                        void* stream);
+int rec_tisas_embed_bwd(int64_t n, int32_t dim, int64_t num_rows, const int64_t* ids, const float* d_out, int64_t ld_dout,
+                        float scale, float p, uint64_t seed, uint64_t stream_id, float* rows, int64_t ld_rows, void* stream);
+int rec_tisas_head(int64_t n, int32_t dim, int64_t num_rows, const float* feats, int64_t ld_feats, const int64_t* pos,
+                   const int64_t* neg, const float* table, int64_t ld_table, float* loss2, float* row_loss, float* pos_logits,
+                   float* neg_logits, float* coef_pos, float* coef_neg, float* d_feats, int64_t ld_dfeats, float* d_pos_rows, int64_t ld_dpos, float* d_neg_rows,
+                   int64_t ld_dneg, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

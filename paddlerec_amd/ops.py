@@ -2887,6 +2887,192 @@ def w2v_analogy_topk(a, b, c, W, k=4, status=None, cand=None):
     return values, ids
 
 
+# ------------------------------------------------------------------ TiSASRec: time-interval-aware self-attention
+TISAS_SITES = ("att", "pos_k", "pos_v", "time_k", "time_v")      # order of the streams argument of rec_tisas_attn_*
+
+
+def _tisas_attn_args(q, k, v, tables, tm, log_seqs, H, probs, streams, what):
+    ldq, ldk, ldv = _rows_view(q, "q"), _rows_view(k, "k"), _rows_view(v, "v")
+    _chk(tm, torch.int64, "tm")
+    _chk(log_seqs, torch.int64, "log_seqs")
+    if log_seqs.dim() != 2 or tm.dim() != 3:
+        raise RecError("%s: log_seqs must be [B, L] and tm [B, L, L]" % what)
+    B, L = log_seqs.shape
+    D = q.shape[1]
+    if tuple(tm.shape) != (B, L, L) or q.shape[0] != B * L or k.shape != q.shape or v.shape != q.shape or len(tables) != 4:
+        raise RecError("%s: q, k, v must be [B*L, D] and tm [B, L, L] (B %d, L %d; got %s, %s, %s, %s)"
+                       % (what, B, L, tuple(q.shape), tuple(k.shape), tuple(v.shape), tuple(tm.shape)))
+    pos_k, pos_v, time_k, time_v = tables
+    T = time_k.shape[0]
+    for t, n, sh in ((pos_k, "pos_k", (L, D)), (pos_v, "pos_v", (L, D)), (time_k, "time_k", (T, D)), (time_v, "time_v", (T, D))):
+        _chk(t, torch.float32, n, sh)
+    if len(probs) != 3 or len(streams) != 5:
+        raise RecError("%s: probs is (attention, position, time) and streams one per TISAS_SITES" % what)
+    tp = (C.c_void_p * 4)(*[t.data_ptr() for t in tables])
+    pr = (C.c_float * 3)(*[float(x) for x in probs])
+    st = (C.c_uint64 * 5)(*[int(x) for x in streams])
+    return B, L, D, T, ldq, ldk, ldv, tp, pr, st
+
+
+def tisas_attn_fwd(q, k, v, tables, tm, log_seqs, H, scale, probs=(0.0, 0.0, 0.0), seed=0, streams=(0, 0, 0, 0, 0),
+                   status=None, out=None):
+    """TiSASRec's attention without the [B, L, L, D] relation tensors (rec_tisas_attn_fwd).  q, k, v [B*L, D] views with a
+    row stride; tables = (pos_k, pos_v [L, D], time_k, time_v [T, D]); tm int64 [B, L, L]; log_seqs int64 [B, L]; probs =
+    dropout on (weights, position rows, time rows); streams: one mask stream per TISAS_SITES.
+    -> (out [B*L, D], lse [B, H, L])."""
+    B, L, D, T, ldq, ldk, ldv, tp, pr, st = _tisas_attn_args(q, k, v, tables, tm, log_seqs, H, probs, streams, "tisas_attn_fwd")
+    if out is None:
+        out = torch.empty(B * L, D, dtype=torch.float32, device=q.device)
+    ldo = _rows_view(out, "out")
+    if tuple(out.shape) != (B * L, D):
+        raise RecError("tisas_attn_fwd: out must be [B*L, D]")
+    lse = torch.empty(B, int(H), L, dtype=torch.float32, device=q.device)
+    check(lib().rec_tisas_attn_fwd(B, L, int(H), D, T, _p(q), ldq, _p(k), ldk, _p(v), ldv, tp, _p(tm), _p(log_seqs),
+                                   float(scale), pr, int(seed), st, _p(out), ldo, _p(lse), _p(status), _stream()),
+          "rec_tisas_attn_fwd")
+    return out, lse
+
+
+def tisas_attn_bwd(q, k, v, tables, tm, log_seqs, H, scale, lse, d_out, d_tables, probs=(0.0, 0.0, 0.0), seed=0,
+                   streams=(0, 0, 0, 0, 0), grads=None, accumulate=False, scratch=None):
+    """Backward of tisas_attn_fwd (rec_tisas_attn_bwd).  d_tables: four tensors shaped like tables that receive (accumulate:
+    are added) d_pos_k, d_pos_v, d_time_k, d_time_v.  grads: (dq, dk, dv) views to write or None.  scratch: a dict that
+    keeps the call's buffers (gs, ga [B*H*L*L], partials) between calls.  -> (dq, dk, dv)."""
+    B, L, D, T, ldq, ldk, ldv, tp, pr, st = _tisas_attn_args(q, k, v, tables, tm, log_seqs, H, probs, streams, "tisas_attn_bwd")
+    H = int(H)
+    _chk(lse, torch.float32, "lse", (B, H, L))
+    f32 = dict(dtype=torch.float32, device=q.device)
+    if grads is None:
+        grads = tuple(torch.empty(B * L, D, **f32) for _ in range(3))
+    dq, dk, dv = grads
+    for t, n in ((d_out, "d_out"), (dq, "dq"), (dk, "dk"), (dv, "dv")):
+        _rows_view(t, n)
+        if tuple(t.shape) != (B * L, D):
+            raise RecError("tisas_attn_bwd: %s must be [B*L, D], got %s" % (n, tuple(t.shape)))
+    if len(d_tables) != 4:
+        raise RecError("tisas_attn_bwd: d_tables must hold four tensors")
+    for t, src in zip(d_tables, tables):
+        _chk(t, torch.float32, "d_tables", tuple(src.shape))
+    P = min(B, _lib.REC_TISAS_MAX_PARTIALS)
+    need = (B * H * L * L, B * H * L * L, P * 2 * T * D)
+    scratch = scratch if scratch is not None else {}
+    bufs = scratch.get("bufs")
+    if bufs is None or tuple(b.numel() for b in bufs) != need or bufs[0].device != q.device:
+        bufs = scratch["bufs"] = tuple(torch.empty(max(n, 1), **f32)[:n] for n in need)
+    gs, ga, partials = bufs
+    dp = (C.c_void_p * 4)(*[t.data_ptr() for t in d_tables])
+    check(lib().rec_tisas_attn_bwd(B, L, H, D, T, _p(q), ldq, _p(k), ldk, _p(v), ldv, tp, _p(tm), _p(log_seqs), float(scale), pr,
+                                   int(seed), st, _p(d_out), _view_ld(d_out), _p(lse), _p(gs), _p(ga), _p(dq), _view_ld(dq),
+                                   _p(dk), _view_ld(dk), _p(dv), _view_ld(dv), dp, _p(partials), int(bool(accumulate)),
+                                   _stream()), "rec_tisas_attn_bwd")
+    return dq, dk, dv
+
+
+def affine_layer_norm_fwd(x, gamma, beta, eps, r=None, row_ids=None, sum_out=None, out=None):
+    """y = LN((x + r) * (row_ids != 0)) * gamma + beta over the last axis (rec_affine_layer_norm_fwd).  x, r [m, n] views with
+    a row stride; row_ids int64 [m] or None; sum_out: a [m, n] view (may be x) that receives the masked sum, or None.
+    -> (y, mean [m], rstd [m])."""
+    ldx = _rows_view(x, "x")
+    m, n = x.shape
+    _chk(gamma, torch.float32, "gamma", (n,))
+    _chk(beta, torch.float32, "beta", (n,))
+    _chk(row_ids, torch.int64, "row_ids")
+    if row_ids is not None and row_ids.numel() != m:
+        raise RecError("affine_layer_norm_fwd: row_ids must hold one id per row")
+    for t, name in ((r, "r"), (sum_out, "sum_out"), (out, "out")):
+        if t is not None and (_rows_view(t, name) < 0 or tuple(t.shape) != (m, n)):
+            raise RecError("affine_layer_norm_fwd: %s must have x's shape" % name)
+    if out is None:
+        out = torch.empty(m, n, dtype=torch.float32, device=x.device)
+    mean = torch.empty(m, dtype=torch.float32, device=x.device)
+    rstd = torch.empty(m, dtype=torch.float32, device=x.device)
+    check(lib().rec_affine_layer_norm_fwd(m, n, _p(x), ldx, _p(r), _view_ld(r) if r is not None else 0, _p(gamma), _p(beta),
+                                          float(eps), _p(row_ids), _p(sum_out), _view_ld(sum_out) if sum_out is not None else 0,
+                                          _p(out), _view_ld(out), _p(mean), _p(rstd), _stream()), "rec_affine_layer_norm_fwd")
+    return out, mean, rstd
+
+
+def affine_layer_norm_bwd(t, mean, rstd, gamma, dy, dgamma, dbeta, dy2=None, e1=None, e2=None, row_ids=None, out=None):
+    """Backward of affine_layer_norm_fwd (rec_affine_layer_norm_bwd): t is the masked sum the forward normalised; the
+    incoming gradient is dy + dy2; e1, e2 are further gradients of t.  dgamma, dbeta [n] are written.
+    -> dx [m, n], the gradient of x and of r (out may be dy)."""
+    ldt = _rows_view(t, "t")
+    m, n = t.shape
+    for v_, name in ((mean, "mean"), (rstd, "rstd")):
+        _chk(v_, torch.float32, name, (m,))
+    for v_, name in ((gamma, "gamma"), (dgamma, "dgamma"), (dbeta, "dbeta")):
+        _chk(v_, torch.float32, name, (n,))
+    _chk(row_ids, torch.int64, "row_ids")
+    if out is None:
+        out = torch.empty(m, n, dtype=torch.float32, device=t.device)
+    for v_, name in ((dy, "dy"), (dy2, "dy2"), (e1, "e1"), (e2, "e2"), (out, "out")):
+        if v_ is not None and (_rows_view(v_, name) < 0 or tuple(v_.shape) != (m, n)):
+            raise RecError("affine_layer_norm_bwd: %s must have t's shape" % name)
+    ld = lambda v_: _view_ld(v_) if v_ is not None else 0
+    check(lib().rec_affine_layer_norm_bwd(m, n, _p(t), ldt, _p(mean), _p(rstd), _p(gamma), _p(dy), ld(dy), _p(dy2), ld(dy2),
+                                          _p(e1), ld(e1), _p(e2), ld(e2), _p(row_ids), _p(out), ld(out), _p(dgamma), _p(dbeta),
+                                          _stream()), "rec_affine_layer_norm_bwd")
+    return out
+
+
+def tisas_embed_fwd(ids, table, scale, p=0.0, seed=0, stream=0, status=None, out=None):
+    """out[r] = dropout(table[ids[r]] * scale), a zero row for id 0 (rec_tisas_embed_fwd).  ids int64 (any shape, contiguous);
+    table [N, D] with a row stride.  -> out [ids.numel(), D]."""
+    _chk(ids, torch.int64, "ids")
+    D, ld = _chk_table(table, "table")
+    n = ids.numel()
+    if out is None:
+        out = torch.empty(n, D, dtype=torch.float32, device=table.device)
+    if tuple(out.shape) != (n, D):
+        raise RecError("tisas_embed_fwd: out must be [n, D]")
+    check(lib().rec_tisas_embed_fwd(n, D, table.shape[0], _p(ids), _p(table), ld, float(scale), float(p), int(seed), int(stream),
+                                    _p(out), _rows_view(out, "out"), _p(status), _stream()), "rec_tisas_embed_fwd")
+    return out
+
+
+def tisas_embed_bwd(ids, d_out, num_rows, scale, p=0.0, seed=0, stream=0, out=None):
+    """The gradient rows of the table behind tisas_embed_fwd (rec_tisas_embed_bwd): out[r] = d_out[r] * scale through the
+    same mask, zero for id 0.  out: a [n, D] view with a row stride (rows of the step's gradient buffer) or None."""
+    _chk(ids, torch.int64, "ids")
+    ldd = _rows_view(d_out, "d_out")
+    n, D = d_out.shape
+    if ids.numel() != n:
+        raise RecError("tisas_embed_bwd: one id per row of d_out")
+    if out is None:
+        out = torch.empty(n, D, dtype=torch.float32, device=d_out.device)
+    if tuple(out.shape) != (n, D):
+        raise RecError("tisas_embed_bwd: out must be [n, D]")
+    check(lib().rec_tisas_embed_bwd(n, D, int(num_rows), _p(ids), _p(d_out), ldd, float(scale), float(p), int(seed), int(stream),
+                                    _p(out), _rows_view(out, "out"), _stream()), "rec_tisas_embed_bwd")
+    return out
+
+
+def tisas_head(feats, pos, neg, table, status=None, d_pos_rows=None, d_neg_rows=None):
+    """TiSASRec's training head (rec_tisas_head): both dot products per position, the two masked BCE means with the selected
+    count taken on the device, d(feats) and the gradient rows of the pos / neg lookups.  feats [n, D] view; pos, neg int64
+    [n]; table [N, D].  -> (loss2 [2] = loss, selected count; d_feats [n, D]; coef_pos [n]; coef_neg [n]; row_loss [n];
+    pos_logits [n]; neg_logits [n])."""
+    ldf = _rows_view(feats, "feats")
+    n, D = feats.shape
+    Dt, ldt = _chk_table(table, "table")
+    _chk(pos, torch.int64, "pos")
+    _chk(neg, torch.int64, "neg")
+    if Dt != D or pos.numel() != n or neg.numel() != n:
+        raise RecError("tisas_head: feats [n, D], pos / neg [n] and table [N, D] do not fit")
+    f32 = dict(dtype=torch.float32, device=feats.device)
+    loss2, row_loss = torch.empty(2, **f32), torch.empty(n, **f32)
+    cp, cn, d_feats = torch.empty(n, **f32), torch.empty(n, **f32), torch.empty(n, D, **f32)
+    pl, nl = torch.empty(n, **f32), torch.empty(n, **f32)
+    for t, name in ((d_pos_rows, "d_pos_rows"), (d_neg_rows, "d_neg_rows")):
+        if t is not None and (_rows_view(t, name) < 0 or tuple(t.shape) != (n, D)):
+            raise RecError("tisas_head: %s must be [n, D]" % name)
+    ld = lambda t: _view_ld(t) if t is not None else 0
+    check(lib().rec_tisas_head(n, D, table.shape[0], _p(feats), ldf, _p(pos), _p(neg), _p(table), ldt, _p(loss2), _p(row_loss),
+                               _p(pl), _p(nl), _p(cp), _p(cn), _p(d_feats), D, _p(d_pos_rows), ld(d_pos_rows), _p(d_neg_rows), ld(d_neg_rows),
+                               _p(status), _stream()), "rec_tisas_head")
+    return loss2, d_feats, cp, cn, row_loss, pl, nl
+
+
 # ------------------------------------------------------------------ xDeepFM CIN (the passes around the GEMM)
 def _chk_f32(t, name):
     if not t.is_cuda:

@@ -908,3 +908,187 @@ class Word2vecInferReader:
                 cols = [torch.from_numpy(np.stack([g[i] for g in group])) for i in range(5)]
                 group = []
                 yield tuple(t.contiguous().to(self.device, non_blocking=True) for t in cols[:4]) + (cols[4],)
+
+
+# ---------------------------------------------------------------------------------------------------- TiSASRec (MovieLens)
+def tisas_compute_repos(time_seq, time_span):
+    """movielens_reader.py:123-133 computeRePos, vectorised: |t_i - t_j| clipped to time_span -> int64 [n, n]."""
+    t = np.asarray(time_seq, np.int64)
+    return np.minimum(np.abs(t[:, None] - t[None, :]), int(time_span)).astype(np.int64)
+
+
+def tisas_time_slice(time_set):
+    time_min = min(time_set)
+    return {t: int(round(float(t - time_min))) for t in time_set}
+
+
+def tisas_clean_and_sort(User, time_map):
+    """movielens_reader.py:157-196 cleanAndsort, statement for statement: users and items are numbered in the iteration
+    order of a Python set, every user's times are rescaled by the user's own smallest non-zero gap."""
+    User_filted, user_set, item_set = dict(), set(), set()
+    for user, items in User.items():
+        user_set.add(user)
+        User_filted[user] = items
+        for item in items:
+            item_set.add(item[0])
+    user_map, item_map = dict(), dict()
+    for u, user in enumerate(user_set):
+        user_map[user] = u + 1
+    for i, item in enumerate(item_set):
+        item_map[item] = i + 1
+    for user, items in User_filted.items():
+        User_filted[user] = sorted(items, key=lambda x: x[1])
+    User_res = dict()
+    for user, items in User_filted.items():
+        User_res[user_map[user]] = list(map(lambda x: [item_map[x[0]], time_map[x[1]]], items))
+    time_max = set()
+    for user, items in User_res.items():
+        time_list = list(map(lambda x: x[1], items))
+        time_diff = set()
+        for i in range(len(time_list) - 1):
+            if time_list[i + 1] - time_list[i] != 0:
+                time_diff.add(time_list[i + 1] - time_list[i])
+        time_scale = 1 if len(time_diff) == 0 else min(time_diff)
+        time_min = min(time_list)
+        User_res[user] = list(map(lambda x: [x[0], int(round((x[1] - time_min) / time_scale) + 1)], items))
+        time_max.add(max(set(map(lambda x: x[1], User_res[user]))))
+    return User_res, len(user_set), len(item_set), max(time_max), user_map, item_map
+
+
+def tisas_data_partition(fname):
+    """movielens_reader.py:199-249 data_partition: lines of 4 (user, item, rating, time) or 3 (user, item, time) tab-separated
+    columns; users and items with fewer than 5 events are dropped; the last two events of a user with at least 3 are the
+    valid and the test item.  -> (user_train, user_valid, user_test, usernum, itemnum, timenum, user_map, item_map)."""
+    from collections import defaultdict
+    User, user_count, item_count, time_set = defaultdict(list), defaultdict(int), defaultdict(int), set()
+
+    def rows():
+        with open(fname, "r") as f:
+            for line in f:
+                cols = line.rstrip().split("\t")
+                if len(cols) == 4:
+                    u, i, _, ts = cols
+                else:
+                    u, i, ts = cols
+                yield int(u), int(i), ts
+
+    for u, i, _ in rows():
+        user_count[u] += 1
+        item_count[i] += 1
+    for u, i, ts in rows():
+        ts = float(ts)
+        if user_count[u] < 5 or item_count[i] < 5:
+            continue
+        time_set.add(ts)
+        User[u].append([i, ts])
+    User, usernum, itemnum, timenum, user_map, item_map = tisas_clean_and_sort(User, tisas_time_slice(time_set))
+    user_train, user_valid, user_test = {}, {}, {}
+    for user in User:
+        if len(User[user]) < 3:
+            user_train[user], user_valid[user], user_test[user] = User[user], [], []
+        else:
+            user_train[user], user_valid[user], user_test[user] = User[user][:-2], [User[user][-2]], [User[user][-1]]
+    return user_train, user_valid, user_test, usernum, itemnum, timenum, user_map, item_map
+
+
+class TisasDataset:
+    """models/recall/tisas/movielens_reader.py RecDataset, a map-style dataset.  mode "train": __getitem__ IGNORES its index
+    and draws the user and the negatives from the generator seeded 2021 in the constructor (the reference seeds the global
+    np.random; a RandomState of the same seed yields the same draws) -> (seq [L], time_matrix [L, L], pos [L], neg [L]);
+    mode "test": (seq [L], time_matrix [L, L], item_idx [101]) of test user idx, the test item first, then 100 sampled
+    negatives.  All int64."""
+
+    def __init__(self, file_list, maxlen, time_span, mode="test"):
+        self.rng = np.random.RandomState(2021)
+        (self.user_train, self.user_valid, self.user_test, self.usernum, self.itemnum, self.timenum, self.user_map,
+         self.item_map) = tisas_data_partition(list(file_list)[0])
+        self.maxlen, self.time_span, self.mode = int(maxlen), int(time_span), mode
+        self.relation_matrix = {}
+        for user in range(1, self.usernum + 1):                 # Relation(): the matrix of user_train[:-1]
+            time_seq = np.zeros([self.maxlen], dtype=np.int64)
+            idx = self.maxlen - 1
+            for i in reversed(self.user_train[user][:-1]):
+                time_seq[idx] = i[1]
+                idx -= 1
+                if idx == -1:
+                    break
+            self.relation_matrix[user] = tisas_compute_repos(time_seq, self.time_span)
+        if self.mode == "test":
+            if self.usernum > 10000:
+                raise ValueError("TiSASRec test reader: more than 10000 users — the reference samples them with "
+                                 "np.random.sample(user_idx, 10000), a call that takes no second argument and cannot run "
+                                 "(movielens_reader.py:45-46); this branch has no behaviour to mirror")
+            self.test_users = [u for u in range(1, self.usernum + 1) if len(self.user_train[u]) > 0]
+
+    def __len__(self):
+        return len(self.user_train) if self.mode == "train" else len(self.test_users)
+
+    def _random_neq(self, lo, hi, s):
+        t = self.rng.randint(lo, hi)
+        while t in s:
+            t = self.rng.randint(lo, hi)
+        return t
+
+    def sample(self, user):
+        L = self.maxlen
+        seq, time_seq, pos, neg = (np.zeros([L], dtype=np.int64) for _ in range(4))
+        nxt = self.user_train[user][-1][0]
+        idx = L - 1
+        ts = set(map(lambda x: x[0], self.user_train[user]))
+        for i in reversed(self.user_train[user][:-1]):
+            seq[idx], time_seq[idx], pos[idx] = i[0], i[1], nxt
+            if nxt != 0:
+                neg[idx] = self._random_neq(1, self.itemnum + 1, ts)
+            nxt = i[0]
+            idx -= 1
+            if idx == -1:
+                break
+        return seq, self.relation_matrix[user].astype("int64"), pos, neg
+
+    def __getitem__(self, idx):
+        if self.mode == "train":
+            user = self.rng.randint(1, self.usernum + 1)
+            while len(self.user_train[user]) <= 1:
+                user = self.rng.randint(1, self.usernum + 1)
+            return self.sample(user)
+        u = self.test_users[idx]
+        L = self.maxlen
+        seq, time_seq = np.zeros([L], dtype=np.int64), np.zeros([L], dtype=np.int64)
+        idx = L - 1
+        seq[idx], time_seq[idx] = self.user_valid[u][0][0], self.user_valid[u][0][1]
+        idx -= 1
+        for i in reversed(self.user_train[u]):
+            seq[idx], time_seq[idx] = i[0], i[1]
+            idx -= 1
+            if idx == -1:
+                break
+        time_matrix = tisas_compute_repos(time_seq, self.time_span)
+        item_idx = [self.user_test[u][0][0]]
+        rated = set(map(lambda x: x[0], self.user_train[u]))
+        rated.add(self.user_valid[u][0][0])
+        rated.add(0)
+        for _ in range(100):
+            t = self.rng.randint(1, self.itemnum + 1)
+            while t in rated:
+                t = self.rng.randint(1, self.itemnum + 1)
+            item_idx.append(t)
+        return seq, time_matrix, np.array(item_idx, dtype=np.int64)
+
+
+class TisasReader:
+    """The reference's DataLoader over a TisasDataset: indices 0 .. len - 1 in order, batch_size samples stacked, the last
+    partial batch dropped.  ONE dataset serves every epoch (the generator's draws carry on, as in the reference).  Yields
+    tuples of int64 tensors on `device`."""
+
+    def __init__(self, file_list, batch_size, device="cuda", maxlen=50, time_span=256, mode="train"):
+        self.dataset = TisasDataset(file_list, maxlen, time_span, mode)
+        self.batch_size, self.device = int(batch_size), device
+
+    def __len__(self):
+        return len(self.dataset) // self.batch_size
+
+    def __iter__(self):
+        for b in range(len(self)):
+            rows = [self.dataset[b * self.batch_size + j] for j in range(self.batch_size)]
+            yield tuple(torch.from_numpy(np.stack([r[c] for r in rows])).contiguous().to(self.device, non_blocking=True)
+                        for c in range(len(rows[0])))

@@ -10,7 +10,7 @@ What differs by construction: a batch never becomes 28 per-sample NumPy arrays (
 [B,26] / [B,13] device tensors), `loss.backward(); optimizer.step()` is the explicit `train_step` chain of the
 host mirrors, and the AUC buckets stay on the device (read back only when a log line prints them).
 
-    python -m paddlerec_amd.trainer -m <config.yaml> [--model deepfm|fm|ffm|deepfefm|fat_deepffm|wide_deep|dnn|dcn|dcn_v2|gatenet|flen|autofis|din|dien|dmr|bst|xdeepfm|dlrm|mmoe|ple|esmm|escm2|aitm|mind|word2vec] [-o runner.epochs=1 ...] [--infer]
+    python -m paddlerec_amd.trainer -m <config.yaml> [--model deepfm|fm|ffm|deepfefm|fat_deepffm|wide_deep|dnn|dcn|dcn_v2|gatenet|flen|autofis|din|dien|dmr|bst|xdeepfm|dlrm|mmoe|ple|esmm|escm2|aitm|mind|word2vec|tisas] [-o runner.epochs=1 ...] [--infer]
     python -m torch.distributed.run --nproc-per-node G -m paddlerec_amd.trainer -m <config.yaml>     # collective mode
 """
 import argparse
@@ -25,7 +25,7 @@ from . import checkpoint
 logger = logging.getLogger("paddlerec_amd.trainer")
 
 MODELS = ("deepfm", "fm", "ffm", "deepfefm", "fat_deepffm", "wide_deep", "dnn", "dcn", "dcn_v2", "gatenet", "flen", "autofis",
-          "din", "dien", "dmr", "bst", "xdeepfm", "dlrm", "mmoe", "ple", "esmm", "escm2", "aitm", "mind", "word2vec")
+          "din", "dien", "dmr", "bst", "xdeepfm", "dlrm", "mmoe", "ple", "esmm", "escm2", "aitm", "mind", "word2vec", "tisas")
 
 
 # ------------------------------------------------------------------------------------ configuration
@@ -122,6 +122,8 @@ def _dygraph_model(name):
         from .mind import DygraphModel
     elif name == "word2vec":
         from .word2vec import DygraphModel
+    elif name == "tisas":
+        from .tisas import DygraphModel
     else:
         raise ValueError("unknown model %r (known: %s)" % (name, ", ".join(MODELS)))
     return DygraphModel()
@@ -176,6 +178,10 @@ def create_data_loader(config, model, device, mode="train", shard=None):
         rd = reader.Word2vecReader(files, bs, device, dict_path("runner.word_count_dict_path"),
                                    config.get("hyper_parameters.window_size", 5), config.get("hyper_parameters.neg_num", 5))
         return lambda: iter(rd)
+    if model == "tisas":
+        rd = reader.TisasReader(files, bs, device, config.get("hyper_parameters.maxlen"), config.get("hyper_parameters.time_span"),
+                                "train" if mode == "train" else "test")
+        return lambda: iter(rd)                       # ONE dataset: its generator's draws carry across epochs
     if model == "flen":
         return lambda: iter(reader.AvazuReader(files, bs, device, shard=shard))
     if model == "autofis":
@@ -341,7 +347,7 @@ def _apply_optimizer_config(config, model, dy_model):
         logger.info("bst, kept as the reference writes it: %s; preprocess_cmd=%r postprocess_cmd=%r, Dropout(%.2f) with "
                     "the engine's counter-based masks (seed %d)", QUIRKS, dy_model.preprocess_cmd, dy_model.postprocess_cmd,
                     dy_model.dropout_rate, dy_model.dropout_seed)
-    if model in ("mmoe", "ple", "esmm", "escm2", "aitm", "mind", "word2vec"):
+    if model in ("mmoe", "ple", "esmm", "escm2", "aitm", "mind", "word2vec", "tisas"):
         import importlib
         logger.info("%s, kept as the reference writes it: %s", model, importlib.import_module("." + model, __package__).QUIRKS)
         if model == "ple":
