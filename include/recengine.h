@@ -2241,6 +2241,68 @@ int rec_tisas_head(int64_t n, int32_t dim, int64_t num_rows, const float* feats,
                    float* neg_logits, float* coef_pos, float* coef_neg, float* d_feats, int64_t ld_dfeats, float* d_pos_rows, int64_t ld_dpos, float* d_neg_rows,
                    int64_t ld_dneg, int32_t* status, void* stream);
 
+/* ----------------------------------------------------------------------------------------
+ * ENSFM (models/recall/ensfm), the non-sampling factorization machine (csrc/ensfm_ops.hip).  float32; no float atomics;
+ * every sum has a fixed order, so a rerun is bit-identical.  No entry point takes a workspace: what a call needs beyond its
+ * results are buffers of the caller's whose sizes follow from the shapes (partials below).  Arguments are checked on the
+ * host before any launch (REC_EINVAL, the entry named in rec_last_error()); a size of 0 rows returns REC_OK without a launch
+ * after those checks.  C = emb_dim + 2 throughout; emb_dim 1..REC_ENSFM_MAX_DIM.  h = [H_i, 1, 1].  The reference's
+ * [B, I+1, C] `dot` (net.py:87) and its three [B, P, C] tensors (net.py:92-97) are never formed.
+ *
+ * rec_ensfm_tower_fwd: net.py:65-83 for one side.  ids int64 [n, num_fields] into table [num_rows, emb_dim] (ld_table) and
+ *   bias_table [bias_rows] (the reference sizes item_bias one row shorter than all_item_feature_emb):
+ *     s = sum_f table[id_f];  score = (0.5 (s^2 - sum_f table[id_f]^2)) . H_s + sum_f bias_table[id_f] (+ bias[0]; may be NULL)
+ *   out [n, C] (ld_out) = [s, score, 1] (item_layout == 0: p_emb) or [s, 1, score] (item_layout != 0: q_emb).  An id outside a
+ *   table sets REC_FLAG_INDEX_OOB in *status (may be NULL) and contributes zero there.  The same id twice in a row is legal.
+ * rec_ensfm_tower_bwd: from d_out [n, C] (ld_dout; the constant column is not read):
+ *     rows[r num_fields + f] = d_out[r, :emb_dim] + dscore_r H_s o (s_r - table[id_f])      [n num_fields, emb_dim] (ld_rows):
+ *                              the gradient row of every lookup, rec_grad_layout{1,0,0} for rec_adagrad_rows; zero for a bad id
+ *     dscore [n]: the gradient of every bias lookup of row r, read through rec_grad_layout{num_fields,0,0} with emb_dim 1
+ *     dH_s [emb_dim] (+)= sum_r dscore_r 0.5 (s_r^2 - sum_f e_f^2);  dbias [1] (may be NULL) (+)= sum_r dscore_r
+ *   accumulate != 0 adds to what dH_s / dbias hold (H_s is shared by the two towers).  partials holds
+ *   min(ceil(n / 4), REC_ENSFM_MAX_PARTIALS) * (emb_dim + 1) floats: a block sums a fixed slice of the rows, one fold adds the
+ *   blocks.  n == 0 leaves dH_s / dbias as they are.
+ * rec_ensfm_gram: G [cols, cols] = X^T X for X [n, cols] (ldx), cols 1..REC_ENSFM_MAX_DIM + 2.  partials holds
+ *   min(ceil(n / 64), REC_ENSFM_GRAM_MAX_BLOCKS) * cols * cols floats.
+ * rec_ensfm_pos_user: net.py:92-97, dygraph_model.py:50 and their backward in one pass, one block per user.  ur int64
+ *   [batch, max_pos], padded with num_items; p [batch, C], q [num_items + 1, C], G_q = q^T q:
+ *     pos_r[b, j] = m <p[b] o h, q[ur[b, j]]>, m = (ur[b, j] != num_items);  g[b, j] = m (2 (1 - w) pos_r - 2)
+ *     loss_part[b] = sum_j ((1 - w) pos_r^2 - 2 pos_r);  dHi_part[b, :] = p[b, :emb_dim] o sum_j g q[ur[b, j], :emb_dim]
+ *     dP[b, :] = h o sum_j g q[ur[b, j]] + 2 w h o (G_q (p[b] o h))
+ *   pos_r may be NULL.  An id outside [0, num_items] sets REC_FLAG_INDEX_OOB and counts as padding.
+ * rec_ensfm_pos_item: dQ [num_items + 1, C] for ALL rows, the padding row included:
+ *     dQ[i, :] = h o sum_{(b, j) -> i} g[b, j] p[b] + 2 w h o (G_p (q[i] o h))
+ *   n_uniq, uniq_rows, seg_offset, sorted_pos: rec_ids_group of ur viewed as [batch max_pos] with num_rows = num_items + 1 and
+ *   padding_idx = num_items.  One block per item with positives; occurrence i of its list goes to partial i % 16, each in
+ *   ascending i, folded in a fixed tree, so an item in every list is 16 chains and not one.
+ * rec_ensfm_loss: loss[0] = w sum_{c, c'} G_q G_p h h + sum_b loss_part[b] (dygraph_model.py:40-51);
+ *     dH_i[d] = sum_b dHi_part[b, d] + 2 w sum_c' G_q[d, c'] G_p[d, c'] h[c'].
+ * rec_ensfm_score: pre [batch, num_rows] (ld_pre) = (p o h) q^T for --infer (net.py:87-90), LDS-tiled.
+ * ---------------------------------------------------------------------------------------- */
+#define REC_ENSFM_MAX_DIM 128
+#define REC_ENSFM_MAX_PARTIALS 1024
+#define REC_ENSFM_GRAM_MAX_BLOCKS 256
+
+int rec_ensfm_tower_fwd(int64_t n, int32_t num_fields, int32_t emb_dim, int64_t num_rows, int64_t bias_rows, const int64_t* ids,
+                        const float* table, int64_t ld_table, const float* bias_table, const float* H_s, const float* bias,
+                        int32_t item_layout, float* out, int64_t ld_out, int32_t* status, void* stream);
+int rec_ensfm_tower_bwd(int64_t n, int32_t num_fields, int32_t emb_dim, int64_t num_rows, const int64_t* ids, const float* table,
+                        int64_t ld_table, const float* H_s, const float* d_out, int64_t ld_dout, int32_t item_layout, float* rows,
+                        int64_t ld_rows, float* dscore, float* partials, float* dH_s, float* dbias, int32_t accumulate,
+                        void* stream);
+int rec_ensfm_gram(int64_t n, int32_t cols, const float* X, int64_t ldx, float* partials, float* G, void* stream);
+int rec_ensfm_pos_user(int64_t batch, int32_t max_pos, int32_t emb_dim, int64_t num_items, float neg_weight, const int64_t* ur,
+                       const float* p, int64_t ld_p, const float* q, int64_t ld_q, const float* H_i, const float* G_q, float* g,
+                       float* pos_r, float* dP, int64_t ld_dp, float* loss_part, float* dHi_part, int32_t* status, void* stream);
+int rec_ensfm_pos_item(int64_t batch, int32_t max_pos, int32_t emb_dim, int64_t num_items, float neg_weight, const int32_t* n_uniq,
+                       const int64_t* uniq_rows, const int32_t* seg_offset, const int32_t* sorted_pos, const float* g,
+                       const float* p, int64_t ld_p, const float* q, int64_t ld_q, const float* H_i, const float* G_p, float* dQ,
+                       int64_t ld_dq, void* stream);
+int rec_ensfm_loss(int64_t batch, int32_t emb_dim, float neg_weight, const float* G_p, const float* G_q, const float* H_i,
+                   const float* loss_part, const float* dHi_part, float* loss, float* dH_i, void* stream);
+int rec_ensfm_score(int64_t batch, int64_t num_rows, int32_t emb_dim, const float* p, int64_t ld_p, const float* q, int64_t ld_q,
+                    const float* H_i, float* pre, int64_t ld_pre, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

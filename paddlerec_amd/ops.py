@@ -4034,3 +4034,165 @@ def hash_features(field_idx, values, hash_dim=1000001):
     out = (C.c_int64 * n)()
     check(lib().rec_xxh32_hash_mod(arr, idx, n, hash_dim, out), "rec_xxh32_hash_mod")
     return list(out)
+
+
+# ------------------------------------------------------------------ ENSFM (csrc/ensfm_ops.hip)
+def _ensfm_buf(scratch, key, numel, device):
+    """A float32 buffer of the step's, kept in `scratch` (a dict of the caller's, or None) while it is large enough."""
+    t = None if scratch is None else scratch.get(key)
+    if t is None or t.numel() < numel:
+        t = torch.empty(max(int(numel), 1), dtype=torch.float32, device=device)
+        if scratch is not None:
+            scratch[key] = t
+    return t
+
+
+def ensfm_tower_fwd(ids, table, bias_table, H_s, bias=None, item_layout=False, status=None, out=None):
+    """One side of net.py:65-83 (rec_ensfm_tower_fwd): ids int64 [n, F]; table [rows, D]; bias_table [bias_rows] or
+    [bias_rows, 1]; H_s [D] or [D, 1]; bias [1] or None.  -> out [n, D + 2] = [s, score, 1] (user) or [s, 1, score] (item)."""
+    _chk(ids, torch.int64, "ids")
+    if ids.dim() != 2:
+        raise RecError("ensfm_tower_fwd: ids must be [n, F]")
+    D, ld = _chk_table(table, "table")
+    _chk(bias_table, torch.float32, "bias_table")
+    _chk(H_s, torch.float32, "H_s")
+    _chk(bias, torch.float32, "bias")
+    if H_s.numel() != D:
+        raise RecError("ensfm_tower_fwd: H_s must hold D = %d floats" % D)
+    n, F = ids.shape
+    if out is None:
+        out = torch.empty(n, D + 2, dtype=torch.float32, device=table.device)
+    if tuple(out.shape) != (n, D + 2):
+        raise RecError("ensfm_tower_fwd: out must be [n, D + 2]")
+    check(lib().rec_ensfm_tower_fwd(n, F, D, table.shape[0], bias_table.numel(), _p(ids), _p(table), ld, _p(bias_table), _p(H_s),
+                                    _p(bias), int(bool(item_layout)), _p(out), _rows_view(out, "out"), _p(status), _stream()),
+          "rec_ensfm_tower_fwd")
+    return out
+
+
+def ensfm_tower_partials(n, D):
+    """Floats of rec_ensfm_tower_bwd's partials for n rows."""
+    return max(1, min(-(-n // 4), _lib.REC_ENSFM_MAX_PARTIALS)) * (D + 1)
+
+
+def ensfm_tower_bwd(ids, table, H_s, d_out, dH_s, dbias=None, item_layout=False, accumulate=False, scratch=None, rows=None,
+                    dscore=None):
+    """rec_ensfm_tower_bwd -> (rows [n F, D]: the gradient row of every lookup; dscore [n]: the gradient of every bias lookup
+    of a row).  dH_s [D] and dbias [1] (or None) are written, or added to with accumulate."""
+    _chk(ids, torch.int64, "ids")
+    D, ld = _chk_table(table, "table")
+    n, F = ids.shape
+    ldd = _rows_view(d_out, "d_out")
+    if tuple(d_out.shape) != (n, D + 2):
+        raise RecError("ensfm_tower_bwd: d_out must be [n, D + 2]")
+    _chk(H_s, torch.float32, "H_s")
+    _chk(dH_s, torch.float32, "dH_s")
+    _chk(dbias, torch.float32, "dbias")
+    if H_s.numel() != D or dH_s.numel() != D:
+        raise RecError("ensfm_tower_bwd: H_s and dH_s must hold D = %d floats" % D)
+    dev = table.device
+    if rows is None:
+        rows = torch.empty(n * F, D, dtype=torch.float32, device=dev)
+    if dscore is None:
+        dscore = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
+    if tuple(rows.shape) != (n * F, D) or dscore.numel() < n:
+        raise RecError("ensfm_tower_bwd: rows must be [n F, D] and dscore [n]")
+    part = _ensfm_buf(scratch, "tower_partials", ensfm_tower_partials(n, D), dev)
+    check(lib().rec_ensfm_tower_bwd(n, F, D, table.shape[0], _p(ids), _p(table), ld, _p(H_s), _p(d_out), ldd,
+                                    int(bool(item_layout)), _p(rows), _rows_view(rows, "rows"), _p(dscore), _p(part), _p(dH_s),
+                                    _p(dbias), int(bool(accumulate)), _stream()), "rec_ensfm_tower_bwd")
+    return rows, dscore
+
+
+def ensfm_gram(X, scratch=None, out=None):
+    """G = X^T X (rec_ensfm_gram) for a [n, C] view X -> [C, C]."""
+    ldx = _rows_view(X, "X")
+    n, Cc = X.shape
+    if out is None:
+        out = torch.empty(Cc, Cc, dtype=torch.float32, device=X.device)
+    _chk(out, torch.float32, "out", (Cc, Cc))
+    if n == 0:
+        return out.zero_()                               # nothing is launched for an empty X
+    part = _ensfm_buf(scratch, "gram_partials", min(-(-n // 64), _lib.REC_ENSFM_GRAM_MAX_BLOCKS) * Cc * Cc, X.device)
+    check(lib().rec_ensfm_gram(n, Cc, _p(X), ldx, _p(part), _p(out), _stream()), "rec_ensfm_gram")
+    return out
+
+
+def _ensfm_pq(p, q, H_i, what):
+    ldp, ldq = _rows_view(p, "p"), _rows_view(q, "q")
+    _chk(H_i, torch.float32, "H_i")
+    D = H_i.numel()
+    if p.shape[1] != D + 2 or q.shape[1] != D + 2:
+        raise RecError("%s: p and q must have D + 2 = %d columns" % (what, D + 2))
+    return D, ldp, ldq
+
+
+def ensfm_pos_user(ur, p, q, H_i, G_q, neg_weight, status=None, want_pos_r=False):
+    """The positives, user-owned (rec_ensfm_pos_user): ur int64 [B, P] padded with I = q.shape[0] - 1.
+    -> (g [B, P], dP [B, C], loss_part [B], dHi_part [B, D], pos_r [B, P] or None)."""
+    _chk(ur, torch.int64, "ur")
+    D, ldp, ldq = _ensfm_pq(p, q, H_i, "ensfm_pos_user")
+    _chk(G_q, torch.float32, "G_q", (D + 2, D + 2))
+    if ur.dim() != 2 or ur.shape[0] != p.shape[0]:
+        raise RecError("ensfm_pos_user: ur must be [B, P] with one row per row of p")
+    B, P = ur.shape
+    f32 = dict(dtype=torch.float32, device=p.device)
+    g, dP = torch.empty(B, P, **f32), torch.empty(B, D + 2, **f32)
+    loss_part, dHi_part = torch.empty(max(B, 1), **f32), torch.empty(max(B, 1), D, **f32)
+    pos_r = torch.empty(B, P, **f32) if want_pos_r else None
+    check(lib().rec_ensfm_pos_user(B, P, D, q.shape[0] - 1, float(neg_weight), _p(ur), _p(p), ldp, _p(q), ldq, _p(H_i), _p(G_q),
+                                   _p(g), _p(pos_r), _p(dP), D + 2, _p(loss_part), _p(dHi_part), _p(status), _stream()),
+          "rec_ensfm_pos_user")
+    return g, dP, loss_part, dHi_part, pos_r
+
+
+def ensfm_pos_item(groups, g, p, q, H_i, G_p, neg_weight, out=None):
+    """The positives, item-owned (rec_ensfm_pos_item): groups = ids_group(ur.view(-1), I + 1, I, ...); g [B, P] of
+    ensfm_pos_user.  -> dQ [I + 1, C] for all rows."""
+    D, ldp, ldq = _ensfm_pq(p, q, H_i, "ensfm_pos_item")
+    _chk(G_p, torch.float32, "G_p", (D + 2, D + 2))
+    _chk(g, torch.float32, "g")
+    B = p.shape[0]
+    if g.dim() != 2 or g.shape[0] != B or groups.n != g.numel():
+        raise RecError("ensfm_pos_item: g must be [B, P] and groups the grouping of its B P positions")
+    if out is None:
+        out = torch.empty(q.shape[0], D + 2, dtype=torch.float32, device=q.device)
+    if tuple(out.shape) != (q.shape[0], D + 2):
+        raise RecError("ensfm_pos_item: out must be [I + 1, D + 2]")
+    check(lib().rec_ensfm_pos_item(B, g.shape[1], D, q.shape[0] - 1, float(neg_weight), _p(groups.n_uniq), _p(groups.uniq_rows),
+                                   _p(groups.seg_offset), _p(groups.sorted_pos), _p(g), _p(p), ldp, _p(q), ldq, _p(H_i), _p(G_p),
+                                   _p(out), _rows_view(out, "out"), _stream()), "rec_ensfm_pos_item")
+    return out
+
+
+def ensfm_loss(G_p, G_q, H_i, loss_part, dHi_part, neg_weight, B, loss=None, dH_i=None):
+    """rec_ensfm_loss -> (loss [1], dH_i [D])."""
+    for t, name in ((G_p, "G_p"), (G_q, "G_q"), (H_i, "H_i"), (loss_part, "loss_part"), (dHi_part, "dHi_part")):
+        _chk(t, torch.float32, name)
+    D = H_i.numel()
+    if G_p.numel() != (D + 2) ** 2 or G_q.numel() != (D + 2) ** 2 or loss_part.numel() < B or dHi_part.numel() < B * D:
+        raise RecError("ensfm_loss: G_p, G_q [D + 2, D + 2], loss_part [B] and dHi_part [B, D] do not fit")
+    if loss is None:
+        loss = torch.empty(1, dtype=torch.float32, device=H_i.device)
+    if dH_i is None:
+        dH_i = torch.empty(D, dtype=torch.float32, device=H_i.device)
+    _chk(loss, torch.float32, "loss")
+    _chk(dH_i, torch.float32, "dH_i")
+    if dH_i.numel() != D:
+        raise RecError("ensfm_loss: dH_i must hold D floats")
+    check(lib().rec_ensfm_loss(int(B), D, float(neg_weight), _p(G_p), _p(G_q), _p(H_i), _p(loss_part), _p(dHi_part), _p(loss),
+                               _p(dH_i), _stream()), "rec_ensfm_loss")
+    return loss, dH_i
+
+
+def ensfm_score(p, q, H_i, out=None):
+    """pre [B, I + 1] = (p o h) q^T (rec_ensfm_score): the model's output for --infer; `dot` is never formed."""
+    D, ldp, ldq = _ensfm_pq(p, q, H_i, "ensfm_score")
+    B, rows = p.shape[0], q.shape[0]
+    if out is None:
+        out = torch.empty(B, rows, dtype=torch.float32, device=p.device)
+    if tuple(out.shape) != (B, rows):
+        raise RecError("ensfm_score: out must be [B, I + 1]")
+    check(lib().rec_ensfm_score(B, rows, D, _p(p), ldp, _p(q), ldq, _p(H_i), _p(out), _rows_view(out, "out"), _stream()),
+          "rec_ensfm_score")
+    return out

@@ -1092,3 +1092,116 @@ class TisasReader:
             rows = [self.dataset[b * self.batch_size + j] for j in range(self.batch_size)]
             yield tuple(torch.from_numpy(np.stack([r[c] for r in rows])).contiguous().to(self.device, non_blocking=True)
                         for c in range(len(rows[0])))
+
+
+# ------------------------------------------------------------------ ENSFM (models/recall/ensfm/movielens_reader.py)
+class EnsfmDataset:
+    """LoadData + RecDataset of the reference's movielens_reader.py over <data_root>/train.csv and test.csv, whose lines are
+    `<user features joined by '-'>,<item features joined by '-'>`.  No scipy: the reference's two csr_matrix user-item
+    sets (Train_data, Test_data) are kept as plain (user id, item id) arrays, which is all infer.py reads of them.
+
+      * user_field_M / item_field_M: the largest feature id of TRAIN + 1 (movielens_reader.py:75-97);
+      * items, then users, are numbered in order of first appearance over train.csv then test.csv (:99-157);
+      * item_map_list [I + 1, Fi]: every item's features in id order, then item 0's features AGAIN as row I, the padding item
+        (:60-68);
+      * user_train [U, Fu] / item_train [U, P]: one row per user with train positives in order of first appearance, the
+        positives in file order, padded with I to the longest list (:184-198);
+      * user_test [n_test_lines, Fu]: the user features of EVERY test line, duplicates included (:227-229).
+    __getitem__ as the reference: train -> (user_train[i], item_map_list, item_train[i], I), test -> (user_test[i],
+    item_map_list)."""
+
+    def __init__(self, file_list, mode="train"):
+        root = os.path.dirname(file_list[0]) if not os.path.isdir(file_list[0]) else file_list[0]
+        self.trainfile, self.testfile = os.path.join(root, "train.csv"), os.path.join(root, "test.csv")
+        self.mode = mode
+        rows = {f: self._read(f) for f in (self.trainfile, self.testfile)}
+        tr = rows[self.trainfile]
+        self.user_field_M = max(max(int(x) for x in u.split("-")) for u, _ in tr) + 1
+        self.item_field_M = max(max(int(x) for x in i.split("-")) for _, i in tr) + 1
+        self.binded_items, self.binded_users = {}, {}
+        for col, table in ((1, self.binded_items), (0, self.binded_users)):
+            for f in (self.trainfile, self.testfile):
+                for r in rows[f]:
+                    if r[col] not in table:
+                        table[r[col]] = len(table)
+        self.item_bind_M, self.user_bind_M = len(self.binded_items), len(self.binded_users)
+        feats = lambda key: [int(x) for x in key.strip().split("-")]
+        items = sorted(self.binded_items, key=self.binded_items.get)
+        # movielens_reader.py:66-68: item 0's features again, as the row of the padding id I
+        self.item_map_list = np.asarray([feats(k) for k in items] + [feats(items[0])], np.int64)
+        positives = {}
+        for u, i in tr:
+            positives.setdefault(self.binded_users[u], []).append(self.binded_items[i])
+        self.max_positive_len = max(len(v) for v in positives.values())
+        users = sorted(self.binded_users, key=self.binded_users.get)
+        self.user_train = np.asarray([feats(users[uid]) for uid in positives], np.int64)
+        self.item_train = np.full((len(positives), self.max_positive_len), self.item_bind_M, np.int64)
+        for r, lst in enumerate(positives.values()):
+            self.item_train[r, :len(lst)] = lst
+        self.user_test = np.asarray([feats(u) for u, _ in rows[self.testfile]], np.int64)
+        pairs = lambda rs: np.asarray(sorted({(self.binded_users[u], self.binded_items[i]) for u, i in rs}), np.int64).reshape(-1, 2)
+        self.train_pairs, self.test_pairs = pairs(tr), pairs(rows[self.testfile])     # the non-zeros of Train_data / Test_data
+        self._masks = None
+
+    @staticmethod
+    def _read(path):
+        with open(path) as f:
+            return [tuple(ln.strip().split(",")[:2]) for ln in f if ln.strip()]
+
+    def __len__(self):
+        return len(self.user_train) if self.mode == "train" else len(self.user_test)
+
+    def __getitem__(self, idx):
+        if self.mode == "train":
+            return self.user_train[idx], self.item_map_list, self.item_train[idx], np.asarray(self.item_bind_M)
+        return self.user_test[idx], self.item_map_list
+
+    def user_ids(self, user_features):
+        """infer.py:186-189: rows of user features -> bound user ids."""
+        return [self.binded_users["-".join(str(int(x)) for x in row)] for row in np.asarray(user_features)]
+
+    def user_masks(self, user_features, device, user_ids=None):
+        """(train_mask, test_mask) bool [B, I] of the users behind rows of user features: infer.py's
+        Train_data[user_id].nonzero() and Test_data[user_id].nonzero().  user_ids (int64 [B] on `device`, from EnsfmReader):
+        the rows' bound ids, so nothing comes back to the host; None: they are looked up from the feature rows."""
+        if self._masks is None or self._masks[0].device != torch.empty(0, device=device).device:
+            dense = []
+            for pr in (self.train_pairs, self.test_pairs):
+                m = torch.zeros(self.user_bind_M, self.item_bind_M, dtype=torch.bool)
+                m[torch.from_numpy(pr[:, 0]), torch.from_numpy(pr[:, 1])] = True
+                dense.append(m.to(device))
+            self._masks = dense
+        if user_ids is None:
+            user_ids = torch.as_tensor(self.user_ids(user_features.cpu().numpy() if torch.is_tensor(user_features) else user_features),
+                                       dtype=torch.int64, device=self._masks[0].device)
+        return self._masks[0][user_ids], self._masks[1][user_ids]
+
+
+class EnsfmReader:
+    """The reference's DataLoader over an EnsfmDataset: indices in order, batch_size samples stacked, the last partial batch
+    dropped.  The item attribute matrix goes to the device ONCE; every batch carries the same tensor behind a leading axis of
+    length 1 (the reference stacks B copies and create_feeds takes copy 0: dygraph_model.py:33-35)."""
+
+    def __init__(self, file_list, batch_size, device="cuda", mode="train"):
+        self.dataset = EnsfmDataset(file_list, mode)
+        self.batch_size, self.device = int(batch_size), device
+        self.item_attribute = torch.from_numpy(self.dataset.item_map_list).contiguous().to(device)
+        self.item_bind_M = torch.full((1,), self.dataset.item_bind_M, dtype=torch.int64)      # a host scalar: it stays there
+        self.test_user_ids = None
+        if mode != "train":                                   # the bound id of every test line, on the device once
+            self.test_user_ids = torch.as_tensor(self.dataset.user_ids(self.dataset.user_test), dtype=torch.int64).to(device)
+
+    def __len__(self):
+        return len(self.dataset) // self.batch_size
+
+    def __iter__(self):
+        d, bs = self.dataset, self.batch_size
+        for b in range(len(self)):
+            sl = slice(b * bs, (b + 1) * bs)
+            if d.mode == "train":
+                yield (torch.from_numpy(d.user_train[sl]).contiguous().to(self.device, non_blocking=True),
+                       self.item_attribute[None], torch.from_numpy(d.item_train[sl]).contiguous().to(self.device, non_blocking=True),
+                       self.item_bind_M)
+            else:
+                yield (torch.from_numpy(d.user_test[sl]).contiguous().to(self.device, non_blocking=True), self.item_attribute[None],
+                       self.test_user_ids[sl])

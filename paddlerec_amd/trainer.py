@@ -10,7 +10,7 @@ What differs by construction: a batch never becomes 28 per-sample NumPy arrays (
 [B,26] / [B,13] device tensors), `loss.backward(); optimizer.step()` is the explicit `train_step` chain of the
 host mirrors, and the AUC buckets stay on the device (read back only when a log line prints them).
 
-    python -m paddlerec_amd.trainer -m <config.yaml> [--model deepfm|fm|ffm|deepfefm|fat_deepffm|wide_deep|dnn|dcn|dcn_v2|gatenet|flen|autofis|din|dien|dmr|bst|xdeepfm|dlrm|mmoe|ple|esmm|escm2|aitm|mind|word2vec|tisas] [-o runner.epochs=1 ...] [--infer]
+    python -m paddlerec_amd.trainer -m <config.yaml> [--model deepfm|fm|ffm|deepfefm|fat_deepffm|wide_deep|dnn|dcn|dcn_v2|gatenet|flen|autofis|din|dien|dmr|bst|xdeepfm|dlrm|mmoe|ple|esmm|escm2|aitm|mind|word2vec|tisas|ensfm] [-o runner.epochs=1 ...] [--infer]
     python -m torch.distributed.run --nproc-per-node G -m paddlerec_amd.trainer -m <config.yaml>     # collective mode
 """
 import argparse
@@ -25,7 +25,8 @@ from . import checkpoint
 logger = logging.getLogger("paddlerec_amd.trainer")
 
 MODELS = ("deepfm", "fm", "ffm", "deepfefm", "fat_deepffm", "wide_deep", "dnn", "dcn", "dcn_v2", "gatenet", "flen", "autofis",
-          "din", "dien", "dmr", "bst", "xdeepfm", "dlrm", "mmoe", "ple", "esmm", "escm2", "aitm", "mind", "word2vec", "tisas")
+          "din", "dien", "dmr", "bst", "xdeepfm", "dlrm", "mmoe", "ple", "esmm", "escm2", "aitm", "mind", "word2vec", "tisas",
+          "ensfm")
 
 
 # ------------------------------------------------------------------------------------ configuration
@@ -124,6 +125,8 @@ def _dygraph_model(name):
         from .word2vec import DygraphModel
     elif name == "tisas":
         from .tisas import DygraphModel
+    elif name == "ensfm":
+        from .ensfm import DygraphModel
     else:
         raise ValueError("unknown model %r (known: %s)" % (name, ", ".join(MODELS)))
     return DygraphModel()
@@ -182,6 +185,11 @@ def create_data_loader(config, model, device, mode="train", shard=None):
         rd = reader.TisasReader(files, bs, device, config.get("hyper_parameters.maxlen"), config.get("hyper_parameters.time_span"),
                                 "train" if mode == "train" else "test")
         return lambda: iter(rd)                       # ONE dataset: its generator's draws carry across epochs
+    if model == "ensfm":
+        rd = reader.EnsfmReader(files, bs, device, "train" if mode == "train" else "test")
+        loader = lambda: iter(rd)                     # ONE reader: the item attributes go to the device once
+        loader.dataset = rd.dataset                   # infer.py reads the user -> train / test item sets from it
+        return loader
     if model == "flen":
         return lambda: iter(reader.AvazuReader(files, bs, device, shard=shard))
     if model == "autofis":
@@ -347,7 +355,7 @@ def _apply_optimizer_config(config, model, dy_model):
         logger.info("bst, kept as the reference writes it: %s; preprocess_cmd=%r postprocess_cmd=%r, Dropout(%.2f) with "
                     "the engine's counter-based masks (seed %d)", QUIRKS, dy_model.preprocess_cmd, dy_model.postprocess_cmd,
                     dy_model.dropout_rate, dy_model.dropout_seed)
-    if model in ("mmoe", "ple", "esmm", "escm2", "aitm", "mind", "word2vec", "tisas"):
+    if model in ("mmoe", "ple", "esmm", "escm2", "aitm", "mind", "word2vec", "tisas", "ensfm"):
         import importlib
         logger.info("%s, kept as the reference writes it: %s", model, importlib.import_module("." + model, __package__).QUIRKS)
         if model == "ple":
@@ -486,6 +494,8 @@ def infer(config, model, device="cuda", kernels=None, comm=None):
     load_path = config.get("runner.infer_load_path", "model_output")
     shard = (comm.rank, comm.world) if world > 1 else None
     loader = create_data_loader(config, model, dy_model.device, "test", shard)
+    if hasattr(loader, "dataset") and hasattr(dy_model_class, "dataset"):
+        dy_model_class.dataset = loader.dataset      # ensfm: infer.py masks the train positives and counts the test ones
     limit = _agreed_batches(config, "test", comm, config.get("runner.infer_batch_size")) if world > 1 else None
     if limit is not None and limit <= 0:
         raise ValueError("test_dataloader is null on at least one rank, please ensure batch size < dataset size!")
