@@ -2303,6 +2303,68 @@ int rec_ensfm_loss(int64_t batch, int32_t emb_dim, float neg_weight, const float
 int rec_ensfm_score(int64_t batch, int64_t num_rows, int32_t emb_dim, const float* p, int64_t ld_p, const float* q, int64_t ld_q,
                     const float* H_i, float* pre, int64_t ld_pre, void* stream);
 
+/* ----------------------------------------------------------------------------------------
+ * NCF (models/recall/ncf): NeuMF, GMF and MLP (csrc/ncf_ops.hip).  float32; no float atomics; every sum has a fixed order and
+ * nothing depends on the order in which blocks run, so a rerun is bit-identical.  Arguments are checked on the host before
+ * any launch (REC_EINVAL, the entry and the argument named in rec_last_error()); batch == 0 returns REC_OK without a launch
+ * after those checks.
+ *
+ * The net ("desc" below) is five arguments of every entry: mf_dim (0: MLP mode), n_fc Linear layers in the tower (0: GMF
+ *   mode), widths: a HOST array of n_fc + 1 int32 (may be NULL when n_fc is 0) with widths[0] = fc_layers[0] (the tower's
+ *   input, even) and widths[l] = the output of Linear l (1..n_fc), num_users and num_items.  half = widths[0] / 2 (0 in GMF
+ *   mode).
+ * Packed tables: a user's MF row and MLP row are ONE row of user_table [num_users, Cu], Cu = mf_dim + half, MF first; the
+ *   items the same in item_table [num_items, Ci], Ci = Cu.  Every table and output takes a row stride (ld >= width; the floats
+ *   between rows are never read or written).
+ * Dense buffer [P] (rec_ncf_dense_numel): for l = 1..n_fc: W_l [widths[l-1], widths[l]] row-major (Paddle's [in, out]), then
+ *   b_l [widths[l]]; then prediction.weight [mf_dim + widths[n_fc]] (MF columns first; mf_dim alone in GMF mode) and
+ *   prediction.bias [1].  EVERY tensor starts at a multiple of 4 floats: its size is rounded up, the padding floats are
+ *   zero, get a zero gradient and so stay zero under rec_adam_dense.
+ * An id outside its table sets REC_FLAG_INDEX_OOB in *status (may be NULL), reads as a zero row and gets a zero gradient row.
+ *
+ * rec_ncf_fused_eligible: *eligible = 1 when rec_ncf_step / rec_ncf_score take the net: n_fc <= REC_NCF_MAX_FC, mf_dim and every
+ *   width <= REC_NCF_MAX_WIDTH, and 4 * (2 P + REC_NCF_TILE * S) <= REC_NCF_LDS_BYTES, where S = the floats of one sample of
+ *   a tile: sum_{l=0..n_fc} (widths[l] | 1) activations, sum_{l=1..n_fc} (widths[l] | 1) deltas, 2 (mf_dim | 1) MF rows,
+ *   dz, the loss term and the two validated ids (2 floats each).  A malformed desc is REC_EINVAL, not "ineligible".
+ * rec_ncf_step: forward, log loss (Paddle's epsilon 1e-4) and backward in ONE launch, then a fold launch.  labels int64 [batch];
+ *   mean_over: the mean's denominator (0 -> batch).  Outputs: pred [batch]; g_user [batch, Cu] (ld_gu) and g_item [batch, Ci]
+ *   (ld_gi): the gradient row of every sample's lookup, rec_grad_layout{1,0,0} for rec_adam_rows_all; partials
+ *   [min(ceil(batch / REC_NCF_TILE), REC_NCF_MAX_BLOCKS), P + 1]: every block's dense gradients and loss sum; g_dense [P] and
+ *   loss [1]: their fold in ascending block order.  Block b takes the tiles b, b + G, ... in order; an element of a dense
+ *   gradient is summed by one owner thread over a tile's samples in ascending order.  An ineligible net is REC_EINVAL.
+ * rec_ncf_score: the same forward alone -> pred [batch].
+ * rec_ncf_gather_fwd / rec_ncf_gather_bwd: the glue of the general route (any tower; they read mf_dim, widths[0] and whether
+ *   n_fc is 0).  Forward: pred_in[b, :mf_dim] = mf_u o mf_i (ld_pred_in; the other columns are not touched: the tower's last
+ *   rec_gemm_f32 writes them) and mlp_in [batch, widths[0]] = [mlp_u, mlp_i] (ld_mlp_in).  pred_in may be NULL when mf_dim is
+ *   0, mlp_in when n_fc is 0.  Backward: from d_pred_in (its first mf_dim columns) and d_mlp_in it writes g_user / g_item as
+ *   rec_ncf_step does.
+ * ---------------------------------------------------------------------------------------- */
+#define REC_NCF_MAX_FC 4
+#define REC_NCF_MAX_WIDTH 128
+#define REC_NCF_TILE 32
+#define REC_NCF_MAX_BLOCKS 512
+#define REC_NCF_LDS_BYTES 65536
+int rec_ncf_dense_numel(int32_t mf_dim, int32_t n_fc, const int32_t* widths, int64_t num_users, int64_t num_items, int64_t* numel);
+int rec_ncf_fused_eligible(int32_t mf_dim, int32_t n_fc, const int32_t* widths, int64_t num_users, int64_t num_items,
+                           int32_t* eligible);
+int rec_ncf_step(int32_t mf_dim, int32_t n_fc, const int32_t* widths, int64_t num_users, int64_t num_items, int64_t batch,
+                 int64_t mean_over, const int64_t* users, const int64_t* items, const int64_t* labels, const float* user_table,
+                 int64_t ld_user, const float* item_table, int64_t ld_item, const float* dense, float* pred, float* g_user,
+                 int64_t ld_gu, float* g_item, int64_t ld_gi, float* partials, float* g_dense, float* loss, int32_t* status,
+                 void* stream);
+int rec_ncf_score(int32_t mf_dim, int32_t n_fc, const int32_t* widths, int64_t num_users, int64_t num_items, int64_t batch,
+                  const int64_t* users, const int64_t* items, const float* user_table, int64_t ld_user, const float* item_table,
+                  int64_t ld_item, const float* dense, float* pred, int32_t* status, void* stream);
+int rec_ncf_gather_fwd(int32_t mf_dim, int32_t n_fc, const int32_t* widths, int64_t num_users, int64_t num_items,
+                       int64_t batch, const int64_t* users, const int64_t* items, const float* user_table, int64_t ld_user,
+                       const float* item_table, int64_t ld_item, float* pred_in, int64_t ld_pred_in, float* mlp_in,
+                       int64_t ld_mlp_in, int32_t* status, void* stream);
+int rec_ncf_gather_bwd(int32_t mf_dim, int32_t n_fc, const int32_t* widths, int64_t num_users, int64_t num_items,
+                       int64_t batch, const int64_t* users, const int64_t* items, const float* user_table, int64_t ld_user,
+                       const float* item_table, int64_t ld_item, const float* d_pred_in, int64_t ld_dpred_in,
+                       const float* d_mlp_in, int64_t ld_dmlp_in, float* g_user, int64_t ld_gu, float* g_item, int64_t ld_gi,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

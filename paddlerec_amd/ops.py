@@ -4196,3 +4196,141 @@ def ensfm_score(p, q, H_i, out=None):
     check(lib().rec_ensfm_score(B, rows, D, _p(p), ldp, _p(q), ldq, _p(H_i), _p(out), _rows_view(out, "out"), _stream()),
           "rec_ensfm_score")
     return out
+
+
+# ------------------------------------------------------------------ NCF (models/recall/ncf, csrc/ncf_ops.hip)
+class NcfDesc:
+    """The five arguments that name the net to every rec_ncf_* entry: mf_dim, n_fc, widths (host int32 [n_fc + 1]), num_users,
+    num_items."""
+
+    def __init__(self, num_users, num_items, mf_dim, widths):
+        widths = [int(w) for w in widths]
+        self.mf_dim, self.n_fc, self.num_users, self.num_items = int(mf_dim), max(len(widths) - 1, 0), int(num_users), int(num_items)
+        self.widths = (C.c_int32 * max(len(widths), 1))(*widths)
+
+    def args(self):
+        return self.mf_dim, self.n_fc, self.widths if self.n_fc > 0 else None, self.num_users, self.num_items
+
+
+def ncf_desc(num_users, num_items, mf_dim, widths):
+    """widths = [fc_layers[0], the outputs of the tower's Linears...] ([] in GMF mode); mf_dim 0 in MLP mode."""
+    return NcfDesc(num_users, num_items, mf_dim, widths)
+
+
+def ncf_dense_layout(mf_dim, widths):
+    """The dense buffer of include/recengine.h -> ([(name, offset, shape)], P): layer_i.weight [in, out], layer_i.bias,
+    prediction.weight [width, 1], prediction.bias; every tensor starts at a multiple of 4 floats."""
+    out, off = [], 0
+    for i in range(1, len(widths)):
+        out.append(("layer_%d.weight" % i, off, (widths[i - 1], widths[i])))
+        off += -(-widths[i - 1] * widths[i] // 4) * 4
+        out.append(("layer_%d.bias" % i, off, (widths[i],)))
+        off += -(-widths[i] // 4) * 4
+    pw = int(mf_dim) + (widths[-1] if len(widths) > 1 else 0)
+    out.append(("prediction.weight", off, (pw, 1)))
+    off += -(-pw // 4) * 4
+    out.append(("prediction.bias", off, (1,)))
+    return out, off + 4
+
+
+def ncf_dense_numel(desc):
+    n = C.c_int64(0)
+    check(lib().rec_ncf_dense_numel(*desc.args(), C.byref(n)), "rec_ncf_dense_numel")
+    return n.value
+
+
+def ncf_fused_eligible(desc):
+    """True when rec_ncf_step / rec_ncf_score take the net (host query, no device needed)."""
+    ok = C.c_int32(0)
+    check(lib().rec_ncf_fused_eligible(*desc.args(), C.byref(ok)), "rec_ncf_fused_eligible")
+    return bool(ok.value)
+
+
+def _ncf_ids(users, items, labels=None):
+    for t, n in ((users, "users"), (items, "items"), (labels, "labels")):
+        _chk(t, torch.int64, n)
+    B = users.numel()
+    if items.numel() != B or (labels is not None and labels.numel() != B):
+        raise RecError("ncf: users, items and labels must have one entry per sample")
+    return B
+
+
+def _ncf_out(t, B, cols, dev, name):
+    if t is None:
+        return torch.empty(B, cols, dtype=torch.float32, device=dev)
+    if t.dim() != 2 or tuple(t.shape) != (B, cols):
+        raise RecError("%s must be [%d, %d]" % (name, B, cols))
+    return t
+
+
+def ncf_partials_numel(B, P):
+    return max(1, min(-(-B // _lib.REC_NCF_TILE), _lib.REC_NCF_MAX_BLOCKS)) * (P + 1)
+
+
+def ncf_step(desc, users, items, labels, user_table, item_table, dense, g_dense, mean_over=0, status=None, pred=None,
+             g_user=None, g_item=None, loss=None, scratch=None):
+    """rec_ncf_step: forward, loss and backward of the whole net in one launch -> (pred [B], g_user [B, Cu], g_item [B, Ci],
+    loss [1]); g_dense [P] is written."""
+    B = _ncf_ids(users, items, labels)
+    Cu, ldu = _chk_table(user_table, "user_table")
+    Ci, ldi = _chk_table(item_table, "item_table")
+    _chk(dense, torch.float32, "dense")
+    _chk(g_dense, torch.float32, "g_dense")
+    P = ncf_dense_numel(desc)
+    if dense.numel() != P or g_dense.numel() != P:
+        raise RecError("ncf_step: dense and g_dense must hold P = %d floats" % P)
+    dev = dense.device
+    if pred is None:
+        pred = torch.empty(B, dtype=torch.float32, device=dev)
+    _chk(pred, torch.float32, "pred")
+    g_user, g_item = _ncf_out(g_user, B, Cu, dev, "g_user"), _ncf_out(g_item, B, Ci, dev, "g_item")
+    if loss is None:
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+    _chk(loss, torch.float32, "loss")
+    part = _ensfm_buf(scratch, "ncf_partials", ncf_partials_numel(B, P), dev)
+    check(lib().rec_ncf_step(*desc.args(), B, int(mean_over), _p(users), _p(items), _p(labels), _p(user_table), ldu,
+                             _p(item_table), ldi, _p(dense), _p(pred), _p(g_user), _rows_view(g_user, "g_user"), _p(g_item),
+                             _rows_view(g_item, "g_item"), _p(part), _p(g_dense), _p(loss), _p(status), _stream()),
+          "rec_ncf_step")
+    return pred, g_user, g_item, loss
+
+
+def ncf_score(desc, users, items, user_table, item_table, dense, status=None, pred=None):
+    """rec_ncf_score: the fused forward alone -> pred [B]."""
+    B = _ncf_ids(users, items)
+    ldu, ldi = _chk_table(user_table, "user_table")[1], _chk_table(item_table, "item_table")[1]
+    _chk(dense, torch.float32, "dense")
+    if dense.numel() != ncf_dense_numel(desc):
+        raise RecError("ncf_score: dense must hold P floats")
+    if pred is None:
+        pred = torch.empty(B, dtype=torch.float32, device=dense.device)
+    _chk(pred, torch.float32, "pred")
+    check(lib().rec_ncf_score(*desc.args(), B, _p(users), _p(items), _p(user_table), ldu, _p(item_table), ldi, _p(dense),
+                              _p(pred), _p(status), _stream()), "rec_ncf_score")
+    return pred
+
+
+def ncf_gather_fwd(desc, users, items, user_table, item_table, pred_in, mlp_in, status=None):
+    """rec_ncf_gather_fwd: mf_u o mf_i -> pred_in[:, :mf_dim]; [mlp_u, mlp_i] -> mlp_in (either may be None in the mode
+    without it).  Both are [B, .] float32 views with any row stride."""
+    B = _ncf_ids(users, items)
+    ldu, ldi = _chk_table(user_table, "user_table")[1], _chk_table(item_table, "item_table")[1]
+    ldp = _rows_view(pred_in, "pred_in") if pred_in is not None else 0
+    ldm = _rows_view(mlp_in, "mlp_in") if mlp_in is not None else 0
+    check(lib().rec_ncf_gather_fwd(*desc.args(), B, _p(users), _p(items), _p(user_table), ldu, _p(item_table), ldi,
+                                   _p(pred_in), ldp, _p(mlp_in), ldm, _p(status), _stream()), "rec_ncf_gather_fwd")
+
+
+def ncf_gather_bwd(desc, users, items, user_table, item_table, d_pred_in, d_mlp_in, g_user=None, g_item=None):
+    """rec_ncf_gather_bwd -> (g_user [B, Cu], g_item [B, Ci]) as ncf_step writes them."""
+    B = _ncf_ids(users, items)
+    Cu, ldu = _chk_table(user_table, "user_table")
+    Ci, ldi = _chk_table(item_table, "item_table")
+    ldp = _rows_view(d_pred_in, "d_pred_in") if d_pred_in is not None else 0
+    ldm = _rows_view(d_mlp_in, "d_mlp_in") if d_mlp_in is not None else 0
+    dev = user_table.device
+    g_user, g_item = _ncf_out(g_user, B, Cu, dev, "g_user"), _ncf_out(g_item, B, Ci, dev, "g_item")
+    check(lib().rec_ncf_gather_bwd(*desc.args(), B, _p(users), _p(items), _p(user_table), ldu, _p(item_table), ldi,
+                                   _p(d_pred_in), ldp, _p(d_mlp_in), ldm, _p(g_user), _rows_view(g_user, "g_user"), _p(g_item),
+                                   _rows_view(g_item, "g_item"), _stream()), "rec_ncf_gather_bwd")
+    return g_user, g_item

@@ -1205,3 +1205,33 @@ class EnsfmReader:
             else:
                 yield (torch.from_numpy(d.user_test[sl]).contiguous().to(self.device, non_blocking=True), self.item_attribute[None],
                        self.test_user_ids[sl])
+
+
+def ncf_parse(file_list):
+    """ncf/movielens_reader.py:26-39: every line `user,item,label`, all int -> three int64 arrays in file order."""
+    cols = ([], [], [])
+    for path in file_list:
+        with open(path, "r") as rf:
+            for line in rf:
+                features = line.strip().split(",")
+                for c in range(3):
+                    cols[c].append(int(features[c]))
+    return tuple(np.asarray(c, dtype=np.int64) for c in cols)
+
+
+class NcfReader:
+    """The reference's DataLoader over ncf/movielens_reader.py: the lines in file order, batch_size at a time, the last batch
+    short when the lines do not divide (an IterableDataset's DataLoader does not drop it).  The three columns go to the device
+    once; a batch is three [b, 1] int64 views."""
+
+    def __init__(self, file_list, batch_size, device="cuda"):
+        self.batch_size = int(batch_size)
+        self.users, self.items, self.labels = (torch.from_numpy(c).to(device) for c in ncf_parse(file_list))
+
+    def __len__(self):
+        return -(-self.users.numel() // self.batch_size)
+
+    def __iter__(self):
+        for b in range(len(self)):
+            sl = slice(b * self.batch_size, (b + 1) * self.batch_size)
+            yield self.users[sl].view(-1, 1), self.items[sl].view(-1, 1), self.labels[sl].view(-1, 1)
