@@ -24,7 +24,8 @@ import math
 
 import torch
 
-from .mtl import ADAM_EPS, BETA1, BETA2, STORES, LazyLoss, _Flat
+from .mtl import ADAM_EPS, BETA1, BETA2, STORES, LazyLoss
+from .net_base import FlatStore, LayerBase, auc_metrics
 
 NUM_THRESHOLDS = 100000                  # dygraph_model.py:71-73: paddle.metric.Auc("ROC", num_thresholds=100000)
 CONSTRAINT_WEIGHT, WEIGHT_DECAY, INFO_DIM = 0.6, 1e-6, 32
@@ -68,15 +69,13 @@ def _xavier(t):
     t.uniform_(-lim, lim)
 
 
-class AITMLayer:
+class AITMLayer(LayerBase):
     """aitm/net.py:63-115.  forward(ids [B, F] int64) -> (pCTR [B], pCVR [B]); train_step(ids, click [B], buy [B], lr) ->
     (loss, pred [B, 2] = pCTR | pCVR).  feature_vocabulary: [[name, size], ...] in the order of the ids' columns."""
 
     def __init__(self, feature_vocabulary, embedding_size, tower_dims=(128, 64, 32), drop_prob=(0.1, 0.3, 0.3),
                  constraint_weight=CONSTRAINT_WEIGHT, device="cuda", kernels=None, dropout_seed=12345):
-        from . import ops
-        self.device = torch.device(device)
-        self.k = kernels if kernels is not None else ops     # tests may inject a stand-in backend (host logic only)
+        self._init_runtime(device, kernels)
         pairs = list(feature_vocabulary.items()) if isinstance(feature_vocabulary, dict) else [tuple(p) for p in feature_vocabulary]
         self.feature_names = [str(n) for n, _ in pairs]       # config order; net.py:71's sorted copy is never used
         self.vocab = [int(s) for _, s in pairs]
@@ -110,7 +109,7 @@ class AITMLayer:
         entries += [("Wqkv", (d, 3 * d)), ("info_layer.0.weight", (d, d)), ("info_layer.0.bias", (d,)),
                     ("click_layer.0.weight", (d, 1)), ("click_layer.0.bias", (1,)),
                     ("conversion_layer.0.weight", (d, 1)), ("conversion_layer.0.bias", (1,))]
-        self.flat = _Flat(entries, self.device)
+        self.flat = FlatStore(entries, self.device)
         self._views = {s: {} for s in STORES}
         for s in STORES:
             v, o = self.flat.view[s], self._views[s]
@@ -129,13 +128,7 @@ class AITMLayer:
         for name, w in self.params.items():
             if name.endswith(".weight"):
                 _xavier(w)
-        self.training = True
-        self.status = self.k.new_status(self.device)
-        self.ws = self.k.Workspace(self.device)
-        self.ws_group = self.k.Workspace(self.device)
-        self.groups = self._pp = None
-        self.step_count = 0
-        self._last = None
+        self._pp = None
 
     # ---------------------------------------------------------------- parameters
     def _table_views(self, t):
@@ -147,40 +140,13 @@ class AITMLayer:
         sd.update(self.params)
         return sd
 
-    def parameters(self):
-        return list(self.state_dict().values())
-
-    def set_dict(self, sd):
-        mine = self.state_dict()
-        for key, v in sd.items():
-            dst = mine[key]
-            dst.copy_(torch.as_tensor(v).to(self.device).reshape(dst.shape))
-
-    set_state_dict = set_dict
-
-    def extra_optimizer_state(self):
-        """checkpoint.py: Adam's moments of every parameter, under the parameter's own name."""
+    def _optimizer_views(self):
+        """Adam's moments of every parameter, under the parameter's own name."""
         out = {}
         for s, t in (("m", self.emb_m), ("v", self.emb_v)):
-            for k, v in self._table_views(t).items():
-                out["mtl.%s.%s" % (s, k)] = v.detach().cpu().numpy().copy()
-            for k in self.params:
-                out["mtl.%s.%s" % (s, k)] = self._views[s][k].detach().cpu().numpy().copy()
+            for k, v in dict(self._table_views(t), **self._views[s]).items():
+                out["mtl.%s.%s" % (s, k)] = v
         return out
-
-    def set_extra_optimizer_state(self, st):
-        for s, t in (("m", self.emb_m), ("v", self.emb_v)):
-            views = dict(self._table_views(t), **self._views[s])
-            for k, dst in views.items():
-                key = "mtl.%s.%s" % (s, k)
-                if key in st:
-                    dst.copy_(torch.as_tensor(st[key]).to(dst.device).reshape(dst.shape))
-
-    def train(self):
-        self.training = True
-
-    def eval(self):
-        self.training = False
 
     # ---------------------------------------------------------------- dropout sites
     def dropout_streams(self, step):
@@ -303,13 +269,11 @@ class AITMLayer:
         """Non-lazy Adam with L2 on every row of every table from dX [B, F*D]: lookup i takes row i of dX viewed as
         [B*F, D]; a lookup the gather refused has row -1, which the grouping drops."""
         k = self.k
-        if self.groups is None or self.groups.n != rows.numel():
-            self.groups = k.IdGroups(rows.numel(), self.device)
         # the grouping flags a -1 row as out of range once more: the same bit the gather has already set in self.status
-        k.ids_group(rows, self.num_rows, None, self.ws_group, None, self.status, self.groups)
+        groups = self._grouped("emb", rows, self.num_rows, None, self.status)
         D = self.embedding_size
-        self._pp = k.segment_partials(self.groups, dX, D, out=self._pp)
-        k.adam_rows_all(self.groups, dX, 1, self.emb, self.emb_m, self.emb_v, self.step_count, lr, BETA1, BETA2, ADAM_EPS,
+        self._pp = k.segment_partials(groups, dX, D, out=self._pp)
+        k.adam_rows_all(groups, dX, 1, self.emb, self.emb_m, self.emb_v, self.step_count, lr, BETA1, BETA2, ADAM_EPS,
                         partials=self._pp, l2=WEIGHT_DECAY)
 
     def last_gradients(self):
@@ -345,9 +309,7 @@ class DygraphModel:
         return ids.contiguous(), click.reshape(-1).contiguous(), buy.reshape(-1).contiguous()
 
     def create_metrics(self, device="cuda"):
-        pair = lambda: (torch.zeros(NUM_THRESHOLDS + 1, dtype=torch.int64, device=device),
-                        torch.zeros(NUM_THRESHOLDS + 1, dtype=torch.int64, device=device))
-        return [pair(), pair()], ["click_auc", "purchase_auc"]
+        return auc_metrics(device, ("click_auc", "purchase_auc"), NUM_THRESHOLDS)
 
     def _auc(self, dy_model, metrics_list, pred, click, buy):
         for col, (m, label) in enumerate(zip(metrics_list, (click, buy))):

@@ -23,7 +23,7 @@ import math
 import torch
 
 from . import ops
-from .din import NUM_THRESHOLDS
+from .net_base import FlatStore, LayerBase, auc_metrics, auc_update, scatter_rows
 
 TABLES = ("hist_item_emb_attr", "hist_cat_emb_attr", "hist_position_emb_attr", "target_item_emb_attr",
           "target_cat_emb_attr", "target_position_emb_attr", "userid_attr")
@@ -40,7 +40,7 @@ QUIRKS = ("preprocess_cmd is read from the key hyper_parameters.postprocess_cmd 
           "has a structurally zero gradient (softmax shift invariance)")
 
 
-class BSTLayer:
+class BSTLayer(LayerBase):
     """bst/net.py:22-75.  forward(userid, hist_item_seq, hist_cat_seq, position_seq, target_item, target_cat,
     target_position) -> predict [B,1]; train_step(feeds, label) -> (loss [1], predict [B,1])."""
 
@@ -48,8 +48,7 @@ class BSTLayer:
                  cat_count, position_count, n_encoder_layers, d_model, d_key, d_value, n_head, dropout_rate, postprocess_cmd,
                  preprocess_cmd, prepostprocess_dropout, d_inner_hid, relu_dropout, layer_sizes, device="cuda", kernels=None,
                  dropout_seed=12345):
-        self.device = torch.device(device)
-        self.k = kernels if kernels is not None else ops     # tests may inject a stand-in backend (host logic only)
+        self._init_runtime(device, kernels)
         widths = (int(item_emb_size), int(cat_emb_size), int(position_emb_size))
         dm, dk, dv, H = int(d_model), int(d_key), int(d_value), int(n_head)
         if sum(widths) != dm:
@@ -87,16 +86,11 @@ class BSTLayer:
         for n, i, o, _ in lin:
             shapes += [(n + ".weight", (i, o)), (n + ".bias", (o,))]
         shapes.append(("bias", (1,)))
-        pad4 = lambda n: (n + 3) // 4 * 4
-        total = sum(pad4(math.prod(sh)) for _, sh in shapes)
-        self._dense, self._dense_grad = torch.zeros(total, **f32), torch.zeros(total, **f32)
-        self._dense_acc = torch.full((total,), ADAGRAD_INIT, **f32)
-        self._gb, o = {}, 0
-        for name, sh in shapes:
-            n = math.prod(sh)
-            for store, buf in ((self.params, self._dense), (self._gb, self._dense_grad), (self._acc, self._dense_acc)):
-                store[name] = buf[o:o + n].view(sh)
-            o += pad4(n)
+        # everything but the tables: one flat buffer each for the values, the gradients and the accumulators ("a")
+        self.flat = FlatStore(shapes, self.device, stores=("p", "g", "a"), fill={"a": ADAGRAD_INIT})
+        self._gb = dict(self.flat.view["g"])
+        self.params.update(self.flat.view["p"])
+        self._acc.update(self.flat.view["a"])
         for n, i, o_, std in lin:
             if std is not None:
                 self.params[n + ".weight"].normal_(0.0, std)
@@ -110,12 +104,6 @@ class BSTLayer:
             self.params["bst.%s.weight" % n].normal_(0.0, std)
         self._packed = {s: (store.pop("bst._qkv.weight"), store.pop("bst._qkv.bias"))
                         for s, store in (("p", self.params), ("g", self._gb), ("a", self._acc))}
-        self.training = True
-        self.status = self.k.new_status(self.device)
-        self.ws, self.ws_group = self.k.Workspace(self.device), self.k.Workspace(self.device)
-        self._groups = {}
-        self.step_count = 0
-        self._last = None
         # the 'd' letters of the four pre / post-process calls, in forward order, own mask streams 0 .. npp-1 of a step;
         # the softmax weights own stream npp and the dropout behind hid2_l stream npp + 1
         self.num_pp_sites = (3 * self.preprocess_cmd + self.postprocess_cmd).count("d")
@@ -125,29 +113,9 @@ class BSTLayer:
     def state_dict(self):
         return dict(self.params)
 
-    def parameters(self):
-        return list(self.params.values())
-
-    def set_dict(self, sd):
-        for key, v in sd.items():
-            self.params[key].copy_(torch.as_tensor(v).to(self.device).reshape(self.params[key].shape))
-
-    set_state_dict = set_dict
-
-    def extra_optimizer_state(self):
-        """checkpoint.py: the Adagrad accumulator of every parameter, under the parameter's own name."""
-        return {"bst.acc." + n: a.detach().cpu().numpy().copy() for n, a in self._acc.items()}
-
-    def set_extra_optimizer_state(self, st):
-        for n, a in self._acc.items():
-            if "bst.acc." + n in st:
-                a.copy_(torch.as_tensor(st["bst.acc." + n]).to(a.device).reshape(a.shape))
-
-    def train(self):
-        self.training = True
-
-    def eval(self):
-        self.training = False
+    def _optimizer_views(self):
+        """The Adagrad accumulator of every parameter, under the parameter's own name."""
+        return {"bst.acc." + n: a for n, a in self._acc.items()}
 
     # ---------------------------------------------------------------- dropout sites
     def dropout_streams(self, step):
@@ -295,11 +263,7 @@ class BSTLayer:
     # ---------------------------------------------------------------- training
     def _adagrad_rows(self, ids, grad, name, lr, row_stride=0):
         k, table = self.k, self.params[name]
-        n = ids.numel()
-        grp = self._groups.get(n)
-        if grp is None:
-            grp = self._groups[n] = k.IdGroups(n, self.device)
-        k.ids_group(ids, table.shape[0], None, self.ws_group, None, self.status, grp)
+        grp = self._grouped(ids.numel(), ids, table.shape[0], None, self.status)      # one IdGroups per id count
         lay = dict(grad_group=1, grad_group_stride=row_stride) if row_stride else {}
         pp = k.segment_partials(grp, grad, table.shape[1], **lay)
         k.adagrad_rows(grp, grad, 1, table, self._acc[name], lr, ADAGRAD_EPS, partials=pp, **lay)
@@ -348,7 +312,8 @@ class BSTLayer:
         self._last = dict(jobs=jobs, dX=dX, dZ=dZ, dz=dz, dqkv=dqkv, d_ctx=d_ctx)
         for idv, gv, name, rs in jobs:
             self._adagrad_rows(idv, gv, name, lr, rs)
-        k.adagrad_dense(self._dense, self._dense_acc, self._dense_grad, lr, ADAGRAD_EPS)
+        f = self.flat.flat
+        k.adagrad_dense(f["p"], f["a"], f["g"], lr, ADAGRAD_EPS)
         return loss, pred
 
     def last_gradients(self):
@@ -356,9 +321,7 @@ class BSTLayer:
         index_add over the recorded gradient rows)."""
         out = {n: v.clone() for n, v in self._gb.items()}
         for idv, gv, name, rs in self._last["jobs"]:
-            tab = self.params[name]
-            rows = torch.as_strided(gv, (idv.numel(), tab.shape[1]), (rs or tab.shape[1], 1), gv.storage_offset())
-            out[name] = torch.zeros_like(tab).index_add_(0, idv, rows)
+            out[name] = scatter_rows(self.params[name], idv, gv, rs or self.params[name].shape[1])
         return out
 
 
@@ -390,14 +353,11 @@ class DygraphModel:
         return t[0], t[1:8]
 
     def create_metrics(self, device="cuda"):
-        stats = (torch.zeros(NUM_THRESHOLDS + 1, dtype=torch.int64, device=device),
-                 torch.zeros(NUM_THRESHOLDS + 1, dtype=torch.int64, device=device))
-        return [stats], ["auc"]
+        return auc_metrics(device)
 
     def _auc(self, dy_model, metrics_list, pred, label):
         if metrics_list:
-            dy_model.k.auc_histogram(pred.contiguous(), label.to(torch.int64).contiguous(), metrics_list[0][0],
-                                     metrics_list[0][1], NUM_THRESHOLDS)
+            auc_update(dy_model.k, metrics_list[0], pred, label)
 
     def train_forward(self, dy_model, metrics_list, batch_data, config):
         label, feeds = self.create_feeds(batch_data, config, dy_model.device)

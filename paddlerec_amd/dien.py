@@ -23,8 +23,8 @@ import math
 
 import torch
 
-from . import ops
-from .din import NUM_THRESHOLDS, _xavier_uniform_
+from .din import _xavier_uniform_
+from .net_base import FlatStore, LayerBase, auc_metrics, auc_update
 
 TABLES = (("hist_item_emb_attr", 0), ("hist_cat_emb_attr", 1), ("target_item_emb_attr", 0), ("target_cat_emb_attr", 1),
           ("target_item_seq_emb_attr", 0), ("target_cat_seq_emb_attr", 1), ("neg_item_seq_emb_attr", 0),
@@ -35,7 +35,7 @@ QUIRKS = ("padding_idx 0 on all eight tables (row 0 is never trained); the atten
           "plain GRUCell instead of AUGRU, last state whatever the length")
 
 
-class DIENLayer:
+class DIENLayer(LayerBase):
     """dien/net.py:21-280.  forward(...) -> (logit [B,1], aux_loss [1])."""
 
     def __init__(self, item_emb_size, cat_emb_size, act, is_sparse, use_DataLoader, item_count, cat_count, device="cuda",
@@ -43,8 +43,7 @@ class DIENLayer:
         if item_emb_size != cat_emb_size:
             raise ValueError("DIEN: item_emb_size (%d) must equal cat_emb_size (%d): the reference's attention GRU starts "
                              "from a state of item_emb_size * 2 columns (net.py:258)" % (item_emb_size, cat_emb_size))
-        self.device = torch.device(device)
-        self.k = kernels if kernels is not None else ops     # tests may inject a stand-in backend (host logic only)
+        self._init_runtime(device, kernels)
         self.item_emb_size, self.cat_emb_size = item_emb_size, cat_emb_size
         self.item_count, self.cat_count = item_count, cat_count
         f32 = dict(dtype=torch.float32, device=self.device)
@@ -72,34 +71,27 @@ class DIENLayer:
             names = [pat % key for key in GRU_KEYS]
             self.gru_names.append(names)
             shapes += [(names[0], (3 * E, E)), (names[1], (3 * E, E)), (names[2], (3 * E,)), (names[3], (3 * E,))]
-        pad4 = lambda n: (n + 3) // 4 * 4            # every view 16-byte aligned (W_hh is read as float4)
-        self._dense = torch.zeros(sum(pad4(math.prod(sh)) for _, sh in shapes), **f32)
-        self._dense_grad = torch.zeros_like(self._dense)
-        self._gb, o = {}, 0
+        self.flat = FlatStore(shapes, self.device, stores=("p", "g"))     # SGD: no moments; W_hh is read as float4
+        self._gb = self.flat.view["g"]
         for name, sh in shapes:
-            n = math.prod(sh)
-            self.params[name] = self._dense[o:o + n].view(sh)
-            self._gb[name] = self._dense_grad[o:o + n].view(sh)
-            o += pad4(n)
+            self.params[name] = self.flat.view["p"][name]
             if name.startswith("linear_") and name.endswith(".weight"):
                 _xavier_uniform_(self.params[name], sh[0], sh[1])
             elif name.startswith("gru"):
                 self.params[name].uniform_(-1.0 / math.sqrt(E), 1.0 / math.sqrt(E))       # Uniform(+-1/sqrt(H))
-        self.status = self.k.new_status(self.device)
-        self.ws, self.ws_group = self.k.Workspace(self.device), self.k.Workspace(self.device)
-        self._groups = {}
-        self.step_count = 0
 
     # ---------------------------------------------------------------- parameters
     def state_dict(self):
         return dict(self.params)
 
     def set_dict(self, sd):
+        mine = {}
         for key, v in sd.items():
             parts = key.split(".")
             if len(parts) == 4 and parts[0] == "gru_net" and parts[2] == "cell":           # gru_net.{l}.cell.weight_ih
                 key = "gru_net.%s_l%s" % (parts[3], parts[1])
-            self.params[key].copy_(torch.as_tensor(v).to(self.device).reshape(self.params[key].shape))
+            mine[key] = v
+        super().set_dict(mine)
 
     def set_attention(self, weights, biases):
         for dst, src in zip(self.attention_w + self.attention_b, list(weights) + list(biases)):
@@ -161,11 +153,7 @@ class DIENLayer:
         return base_lr if step < 410000 else 0.2
 
     def _sgd_rows(self, ids, grad_view, table, lr, row_stride_floats, padding_idx):
-        n = ids.numel()
-        grp = self._groups.get(n)
-        if grp is None:
-            grp = self._groups[n] = self.k.IdGroups(n, self.device)
-        self.k.ids_group(ids.reshape(-1), table.shape[0], padding_idx, self.ws_group, None, self.status, grp)
+        grp = self._grouped(ids.numel(), ids.reshape(-1), table.shape[0], padding_idx, self.status)   # one per id count
         pp = self.k.segment_partials(grp, grad_view, table.shape[1], grad_group=1, grad_group_stride=row_stride_floats)
         self.k.sparse_sgd_rows(grp, grad_view, table, lr, grad_group=1, grad_group_stride=row_stride_floats, partials=pp)
 
@@ -214,7 +202,7 @@ class DIENLayer:
                 (sv["ti"], dz, "item_b_attr", 1, None)]
         for ids, gv, name, rs, pad in jobs:
             self._sgd_rows(ids.contiguous(), gv, p[name + ".weight"], lr, rs, pad)
-        k.sgd_dense(self._dense, self._dense_grad, lr)
+        k.sgd_dense(self.flat.flat["p"], self.flat.flat["g"], lr)
         return cost, pred, aux
 
 
@@ -234,14 +222,11 @@ class DygraphModel:
         return t[0], t[1], t[2], t[3], label, t[5], t[6], t[7], t[8], t[9]
 
     def create_metrics(self, device="cuda"):
-        stats = (torch.zeros(NUM_THRESHOLDS + 1, dtype=torch.int64, device=device),
-                 torch.zeros(NUM_THRESHOLDS + 1, dtype=torch.int64, device=device))
-        return [stats], ["auc"]
+        return auc_metrics(device)
 
     def _auc(self, dy_model, metrics_list, pred, label):
         if metrics_list:
-            dy_model.k.auc_histogram(pred.contiguous(), label.to(torch.int64).contiguous(), metrics_list[0][0],
-                                     metrics_list[0][1], NUM_THRESHOLDS)
+            auc_update(dy_model.k, metrics_list[0], pred, label)
 
     def train_forward(self, dy_model, metrics_list, batch_data, config):
         feeds = self.create_feeds(batch_data, config, dy_model.device)

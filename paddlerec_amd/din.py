@@ -20,6 +20,7 @@ import torch
 
 from . import ops
 from . import ops as _ops
+from .net_base import NUM_THRESHOLDS, auc_metrics, auc_update  # noqa: F401 (NUM_THRESHOLDS is imported from here too)
 
 
 def _xavier_uniform_(t, fan_in, fan_out):
@@ -376,9 +377,6 @@ class DINLayer:
         return loss, pred
 
 
-NUM_THRESHOLDS = 4095  # paddle.metric.Auc default [EXT]
-
-
 class DygraphModel:
     """din/dygraph_model.py:21-113 — same method names; tensors are torch device tensors."""
 
@@ -395,14 +393,11 @@ class DygraphModel:
         return t[0], t[1], t[2], t[3], label, t[5], t[6], t[7]
 
     def create_metrics(self, device="cuda"):
-        stats = (torch.zeros(NUM_THRESHOLDS + 1, dtype=torch.int64, device=device),
-                 torch.zeros(NUM_THRESHOLDS + 1, dtype=torch.int64, device=device))
-        return [stats], ["auc"]
+        return auc_metrics(device)
 
     def _auc(self, dy_model, metrics_list, pred, label):
         if metrics_list:
-            dy_model.k.auc_histogram(pred.contiguous(), label.to(torch.int64).contiguous(), metrics_list[0][0],
-                              metrics_list[0][1], NUM_THRESHOLDS)
+            auc_update(dy_model.k, metrics_list[0], pred, label)
 
     def train_forward(self, dy_model, metrics_list, batch_data, config):
         feeds = self.create_feeds(batch_data, config, dy_model.device)

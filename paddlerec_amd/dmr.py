@@ -22,8 +22,7 @@ import math
 
 import torch
 
-from . import ops
-from .din import NUM_THRESHOLDS
+from .net_base import FlatStore, LayerBase, auc_metrics, auc_update, scatter_rows
 
 USER_FEAT = (("uid", "uid_embeddings_var"), ("cms_segid", "cms_segid_embeddings_var"),
              ("cms_group_id", "cms_group_id_embeddings_var"), ("final_gender_code", "final_gender_code_embeddings_var"),
@@ -44,15 +43,14 @@ QUIRKS = ("a prefix with no valid position is pooled uniformly (1/T) over ALL T 
           "uniform")
 
 
-class DMRLayer:
+class DMRLayer(LayerBase):
     """dmr/net.py:22-554.  forward([sparse [B, 5T+17] i64, price [B,1] f32], is_infer) -> (y_hat [B,1], loss [1])."""
 
     def __init__(self, user_size, cms_segid_size, cms_group_id_size, final_gender_code_size, age_level_size,
                  pvalue_level_size, shopping_level_size, occupation_size, new_user_class_level_size, adgroup_id_size,
                  cate_size, campaign_id_size, customer_size, brand_size, btag_size, pid_size, main_embedding_size,
                  other_embedding_size, history_length=50, device="cuda", kernels=None):
-        self.device = torch.device(device)
-        self.k = kernels if kernels is not None else ops     # tests may inject a stand-in backend (host logic only)
+        self._init_runtime(device, kernels)
         E, O, T = main_embedding_size, other_embedding_size, history_length
         if E % 4 or not 0 < E <= 64:
             raise ValueError("DMR: main_embedding_size %d must be a multiple of 4, at most 64 (rec_dmr_match_loss_*)" % E)
@@ -99,16 +97,10 @@ class DMRLayer:
             shapes += [(n + ".weight", (i, o)), (n + ".bias", (o,))]
         shapes += [(n + "._weight", (c,)) for n, c in prelu]
         shapes += [("inp_layer.weight", (L,)), ("inp_layer.bias", (L,))]
-        pad4 = lambda n: (n + 3) // 4 * 4
-        total = sum(pad4(math.prod(sh)) for _, sh in shapes)
-        self._dense, self._dense_grad = torch.zeros(total, **f32), torch.zeros(total, **f32)
-        self._dense_m, self._dense_v = torch.zeros(total, **f32), torch.zeros(total, **f32)
-        self._gb, o = {}, 0
+        self.flat = FlatStore(shapes, self.device)       # everything but the tables, with Adam's moments: one adam_dense
+        self._gb, self._dense_m = self.flat.view["g"], self.flat.flat["m"]
         for name, sh in shapes:
-            n = math.prod(sh)
-            self.params[name] = self._dense[o:o + n].view(sh)
-            self._gb[name] = self._dense_grad[o:o + n].view(sh)
-            o += pad4(n)
+            self.params[name] = self.flat.view["p"][name]
             if name.endswith("_layer.weight") or name.endswith("_layer2.weight") or name.startswith("query_layer"):
                 if len(sh) == 2:                                                  # nn.Linear: XavierUniform
                     lim = math.sqrt(6.0 / (sh[0] + sh[1]))
@@ -121,43 +113,18 @@ class DMRLayer:
         lim = math.sqrt(6.0 / (E + cate_size))                                    # declared, never used (net.py:236)
         self.params["logits_layer.weight"] = torch.empty(E, cate_size, **f32).uniform_(-lim, lim)
         self.params["logits_layer.bias"] = torch.zeros(cate_size, **f32)
-        self.training = True
-        self.status = self.k.new_status(self.device)
-        self.ws, self.ws_group = self.k.Workspace(self.device), self.k.Workspace(self.device)
-        self._groups, self._ids = {}, {}
-        self.step_count = 0
-        self._last = None
+        self._ids = {}
 
     # ---------------------------------------------------------------- parameters
     def state_dict(self):
         return dict(self.params)
 
-    def set_dict(self, sd):
-        for key, v in sd.items():
-            self.params[key].copy_(torch.as_tensor(v).to(self.device).reshape(self.params[key].shape))
-
-    set_state_dict = set_dict
-
-    def extra_optimizer_state(self):
-        """checkpoint.py: the Adam moments of every table and of the flat dense buffer (the step count is saved there)."""
-        st = {"dmr.dense.m": self._dense_m.cpu().numpy().copy(), "dmr.dense.v": self._dense_v.cpu().numpy().copy()}
+    def _optimizer_views(self):
+        """The Adam moments of the flat dense buffer, gaps included, and of every table (checkpoint.py saves the step)."""
+        st = {"dmr.dense.m": self.flat.flat["m"], "dmr.dense.v": self.flat.flat["v"]}
         for n in self.tables:
-            st["dmr.%s.m" % n], st["dmr.%s.v" % n] = self._tm[n].cpu().numpy().copy(), self._tv[n].cpu().numpy().copy()
+            st["dmr.%s.m" % n], st["dmr.%s.v" % n] = self._tm[n], self._tv[n]
         return st
-
-    def set_extra_optimizer_state(self, st):
-        pairs = [("dmr.dense.m", self._dense_m), ("dmr.dense.v", self._dense_v)]
-        for n in self.tables:
-            pairs += [("dmr.%s.m" % n, self._tm[n]), ("dmr.%s.v" % n, self._tv[n])]
-        for key, dst in pairs:
-            if key in st:
-                dst.copy_(torch.as_tensor(st[key]).to(dst.device).reshape(dst.shape))
-
-    def train(self):
-        self.training = True
-
-    def eval(self):
-        self.training = False
 
     # ---------------------------------------------------------------- forward
     def _const_ids(self, B):
@@ -271,11 +238,7 @@ class DMRLayer:
     # ---------------------------------------------------------------- training
     def _adam_rows(self, ids, grad_view, name, row_stride, step, lr):
         k, table = self.k, self.params[name + ".weight"]
-        n = ids.numel()
-        grp = self._groups.get(n)
-        if grp is None:
-            grp = self._groups[n] = k.IdGroups(n, self.device)
-        k.ids_group(ids, table.shape[0], None, self.ws_group, None, self.status, grp)
+        grp = self._grouped(ids.numel(), ids, table.shape[0], None, self.status)      # one IdGroups per id count
         lay = dict(grad_group=1, grad_group_stride=row_stride)
         pp = k.segment_partials(grp, grad_view, table.shape[1], **lay)
         k.adam_rows_all(grp, grad_view, 1, table, self._tm[name], self._tv[name], step, lr, partials=pp, **lay)
@@ -363,7 +326,8 @@ class DMRLayer:
         self._last = dict(jobs=jobs, d_inp=d_inp, GH=GH, GV=GV, ds1=ds1, ds2=ds2, dz=dz)
         for ids, gv, name, rs in jobs:
             self._adam_rows(ids, gv, name, rs, t, lr)
-        k.adam_dense(self._dense, self._dense_m, self._dense_v, self._dense_grad, t, lr)
+        f = self.flat.flat
+        k.adam_dense(f["p"], f["m"], f["v"], f["g"], t, lr)
         return loss, y_hat, aux, ctr
 
     def last_gradients(self):
@@ -371,10 +335,7 @@ class DMRLayer:
         index_add over the recorded gradient rows)."""
         out = {k: v.clone() for k, v in self._gb.items()}
         for ids, gv, name, rs in self._last["jobs"]:
-            tab = self.params[name + ".weight"]
-            gt = out.setdefault(name + ".weight", torch.zeros_like(tab))
-            rows = torch.as_strided(gv, (ids.numel(), tab.shape[1]), (rs, 1), gv.storage_offset())
-            gt.index_add_(0, ids, rows)
+            out[name + ".weight"] = scatter_rows(self.params[name + ".weight"], ids, gv, rs)      # every table once
         return out
 
 
@@ -395,14 +356,11 @@ class DygraphModel:
         return sparse[:, -1].reshape(-1, 1), [sparse, price.to(torch.float32).reshape(-1, 1)]
 
     def create_metrics(self, device="cuda"):
-        stats = (torch.zeros(NUM_THRESHOLDS + 1, dtype=torch.int64, device=device),
-                 torch.zeros(NUM_THRESHOLDS + 1, dtype=torch.int64, device=device))
-        return [stats], ["auc"]
+        return auc_metrics(device)
 
     def _auc(self, dy_model, metrics_list, pred, label):
         if metrics_list:
-            dy_model.k.auc_histogram(pred.contiguous(), label.to(torch.int64).contiguous(), metrics_list[0][0],
-                                     metrics_list[0][1], NUM_THRESHOLDS)
+            auc_update(dy_model.k, metrics_list[0], pred, label)
 
     def train_forward(self, dy_model, metrics_list, batch_data, config):
         label, feeds = self.create_feeds(batch_data, config, dy_model.device)

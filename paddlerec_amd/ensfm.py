@@ -16,7 +16,7 @@ never reads `pre` (net.py:87-88), and three [B, P, C] tensors for the positives 
 import numpy as np
 import torch
 
-from .mtl import _Flat
+from .net_base import FlatStore, LayerBase
 
 ACC_INIT, ADAGRAD_EPS = 1e-8, 1e-6               # dygraph_model.py:56-59: initial_accumulator_value; Paddle's epsilon [EXT]
 QUIRKS = ("the reader appends item 0's features as row I of item_attribute (movielens_reader.py:66-68), so the padding row of "
@@ -27,16 +27,14 @@ QUIRKS = ("the reader appends item 0's features as row I of item_attribute (movi
           "over every (b, j), padded pairs contributing 0; HR@k divides the hits by min(k, test positives)")
 
 
-class ENSFMLayer:
+class ENSFMLayer(LayerBase):
     """net.py:24-98.  forward(input_u [B, Fu], item_attribute [I+1, Fi], input_ur=None, item_bind_M=None) -> (pre,) or
     (pre, pos_r, q_emb, p_emb, H_i_emb);  train_step(input_u, item_attribute, input_ur, item_bind_M, lr, negative_weight)
     -> loss [1]."""
 
     def __init__(self, user_field_M, item_field_M, embedding_size, device="cuda", kernels=None):
-        from . import ops
         from ._lib import REC_ENSFM_MAX_DIM
-        self.device = torch.device(device)
-        self.k = kernels if kernels is not None else ops
+        self._init_runtime(device, kernels, group_status=True)
         self.user_field_M, self.item_field_M, D = int(user_field_M), int(item_field_M), int(embedding_size)
         self.embedding_size = D
         if not 1 <= D <= REC_ENSFM_MAX_DIM:
@@ -49,22 +47,15 @@ class ENSFMLayer:
                        "all_item_feature_emb.weight": tn(self.item_field_M + 1, D),
                        "user_bias.weight": tn(self.user_field_M, 1), "item_bias.weight": tn(self.item_field_M, 1)}
         self.acc = {n: torch.full_like(t, ACC_INIT) for n, t in self.tables.items()}
-        self.flat = _Flat([("H_i", (D, 1)), ("H_s", (D, 1)), ("bias", (1,))], self.device)    # store "m": the accumulator
+        self.flat = FlatStore([("H_i", (D, 1)), ("H_s", (D, 1)), ("bias", (1,))], self.device,
+                              fill={"m": ACC_INIT})                                         # store "m": the accumulator
         self.params = self.flat.view["p"]
         self.params["H_i"].fill_(0.01)
         self.params["H_s"].fill_(0.01)
-        self.flat.flat["m"].fill_(ACC_INIT)
-        self.training = True
-        self.status = self.k.new_status(self.device)
-        self._group_status = self.k.new_status(self.device)
-        self.ws_group = self.k.Workspace(self.device)
         self._scratch = {}
-        self._groups_u = self._groups_ur = None
         self._item_groups = None                     # (key, item_attribute, its two groupings): made once, the tensor never changes
         self.item_groupings_made = 0
         self._pp = {}
-        self._last = None
-        self.step_count = 0
 
     # ---------------------------------------------------------------- parameters
     def _shown(self, store):
@@ -76,32 +67,9 @@ class ENSFMLayer:
     def state_dict(self):
         return self._shown("p")
 
-    def parameters(self):
-        return list(self.state_dict().values())
-
-    def set_dict(self, sd):
-        mine = self.state_dict()
-        for key, v in sd.items():
-            dst = mine[key]
-            dst.copy_(torch.as_tensor(np.asarray(v) if not torch.is_tensor(v) else v).to(self.device).reshape(dst.shape))
-
-    set_state_dict = set_dict
-
-    def extra_optimizer_state(self):
-        """checkpoint.py: Adagrad's accumulator of every parameter, under the parameter's own name."""
-        return {"ensfm.acc.%s" % k: v.detach().cpu().numpy().copy() for k, v in self._shown("m").items()}
-
-    def set_extra_optimizer_state(self, st):
-        for k, dst in self._shown("m").items():
-            key = "ensfm.acc.%s" % k
-            if key in st:
-                dst.copy_(torch.as_tensor(st[key]).to(dst.device).reshape(dst.shape))
-
-    def train(self):
-        self.training = True
-
-    def eval(self):
-        self.training = False
+    def _optimizer_views(self):
+        """Adagrad's accumulator of every parameter, under the parameter's own name."""
+        return {"ensfm.acc.%s" % k: v for k, v in self._shown("m").items()}
 
     # ---------------------------------------------------------------- forward
     def _check(self, input_u, item_attribute, input_ur=None, item_bind_M=None):
@@ -178,11 +146,9 @@ class ENSFMLayer:
         p_emb, q_emb = self._towers(u, attr)
         G_p, G_q = k.ensfm_gram(p_emb, sc), k.ensfm_gram(q_emb, sc)
         gpos, dP, loss_part, dHi_part, _ = k.ensfm_pos_user(ur, p_emb, q_emb, p["H_i"], G_q, w, status=self.status)
-        if self._groups_ur is None or self._groups_ur.n != ur.numel():
-            self._groups_ur = k.IdGroups(ur.numel(), self.device)
         # padding_idx = I: the padded positions of the lists leave the grouping (net.py:93)
-        k.ids_group(ur.view(-1), I + 1, I, self.ws_group, None, self._group_status, self._groups_ur)
-        dQ = k.ensfm_pos_item(self._groups_ur, gpos, p_emb, q_emb, p["H_i"], G_p, w)
+        groups_ur = self._grouped("ur", ur.view(-1), I + 1, I, self._group_status)
+        dQ = k.ensfm_pos_item(groups_ur, gpos, p_emb, q_emb, p["H_i"], G_p, w)
         loss = torch.empty(1, dtype=torch.float32, device=self.device)
         k.ensfm_loss(G_p, G_q, p["H_i"], loss_part, dHi_part, w, B, loss=loss, dH_i=g["H_i"].view(-1))
         # H_s is shared by both cross terms (net.py:72-73): the user side writes dH_s, the item side adds to it
@@ -193,12 +159,10 @@ class ENSFMLayer:
         # Adagrad over every parameter (dygraph_model.py:54-60), after every gradient has been formed
         fl = self.flat.flat
         k.adagrad_dense(fl["p"], fl["m"], fl["g"], lr, ADAGRAD_EPS)
-        if self._groups_u is None or self._groups_u.n != u.numel():
-            self._groups_u = k.IdGroups(u.numel(), self.device)
-        k.ids_group(u.view(-1), self.user_field_M, None, self.ws_group, None, self._group_status, self._groups_u)
+        groups_u = self._grouped("u", u.view(-1), self.user_field_M, None, self._group_status)
         gv, gb = self._item_side_groups(item_attribute)
-        self._adagrad_rows("user_feature_emb.weight", self._groups_u, rows_u, 1, lr)
-        self._adagrad_rows("user_bias.weight", self._groups_u, dsc_u, Fu, lr)
+        self._adagrad_rows("user_feature_emb.weight", groups_u, rows_u, 1, lr)
+        self._adagrad_rows("user_bias.weight", groups_u, dsc_u, Fu, lr)
         self._adagrad_rows("all_item_feature_emb.weight", gv, rows_v, 1, lr)
         self._adagrad_rows("item_bias.weight", gb, dsc_v, Fi, lr)
         self._last = dict(u=u, attr=attr, rows_u=rows_u, dsc_u=dsc_u, rows_v=rows_v, dsc_v=dsc_v, dP=dP, dQ=dQ, g=gpos,

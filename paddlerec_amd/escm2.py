@@ -74,23 +74,8 @@ class ESCMLayer(MtlLayer):
     def parameters(self):
         return [self.emb.weight] + super().parameters()
 
-    def set_dict(self, sd):
-        sd = dict(sd)
-        w = sd.pop("embedding.weight", None)
-        if w is not None:
-            self.emb.weight.copy_(torch.as_tensor(w).to(self.device).reshape(self.emb.weight.shape))
-        super().set_dict(sd)
-
-    set_state_dict = set_dict
-
-    def extra_optimizer_state(self):
-        out = super().extra_optimizer_state()
-        out.update(self.emb.moments())
-        return out
-
-    def set_extra_optimizer_state(self, st):
-        super().set_extra_optimizer_state(st)
-        self.emb.set_moments(st)
+    def _optimizer_views(self):
+        return dict(super()._optimizer_views(), **self.emb.moment_views())
 
     # ---------------------------------------------------------------- forward
     def predict(self, ids):

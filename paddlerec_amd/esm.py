@@ -13,8 +13,8 @@ reduced loss and the DygraphModel.
     taken, with torch, when something reads it."""
 import torch
 
-from .din import NUM_THRESHOLDS
 from .mtl import ADAM_EPS, BETA1, BETA2, LazyLoss
+from .net_base import auc_metrics, auc_update
 
 
 class EsmLoss(LazyLoss):
@@ -72,14 +72,9 @@ class FieldTable:
         rows = dX.reshape(-1, self.dim)[torch.arange(flat.numel(), device=flat.device)[keep] // self.max_len]
         return torch.zeros_like(self.weight).index_add_(0, flat[keep], rows)
 
-    def moments(self):
-        return {"mtl.m.embedding.weight": self.m.detach().cpu().numpy().copy(),
-                "mtl.v.embedding.weight": self.v.detach().cpu().numpy().copy()}
-
-    def set_moments(self, st):
-        for dst, key in ((self.m, "mtl.m.embedding.weight"), (self.v, "mtl.v.embedding.weight")):
-            if key in st:
-                dst.copy_(torch.as_tensor(st[key]).to(dst.device).reshape(dst.shape))
+    def moment_views(self):
+        """The table's share of its layer's _optimizer_views."""
+        return {"mtl.m.embedding.weight": self.m, "mtl.v.embedding.weight": self.v}
 
 
 def out_list(pred, n_tasks):
@@ -104,15 +99,13 @@ class EsmDygraphModel:
         return ids.contiguous(), click.reshape(-1).contiguous(), buy.reshape(-1).contiguous()
 
     def create_metrics(self, device="cuda"):
-        pair = lambda: (torch.zeros(NUM_THRESHOLDS + 1, dtype=torch.int64, device=device),
-                        torch.zeros(NUM_THRESHOLDS + 1, dtype=torch.int64, device=device))
-        return [pair() for _ in self.METRICS], [n for n, _, _ in self.METRICS]
+        return auc_metrics(device, [n for n, _, _ in self.METRICS])
 
     def _auc(self, dy_model, metrics_list, pred, click, buy):
         G = dy_model.n_tasks
         for m, (_, col, which) in zip(metrics_list, self.METRICS):
             c = 2 * G + 1 if col == "ctcvr" else 2 * col + 1       # column 1 of the prediction
-            dy_model.k.auc_histogram(pred[:, c].contiguous(), buy if which else click, m[0], m[1], NUM_THRESHOLDS)
+            auc_update(dy_model.k, m, pred[:, c], buy if which else click)
 
     def train_forward(self, dy_model, metrics_list, batch_data, config):
         ids, click, buy = self.create_feeds(batch_data, config, dy_model.device)

@@ -15,7 +15,8 @@ import math
 import torch
 
 from .esm import EsmDygraphModel, EsmLoss, FieldTable, out_list
-from .mtl import ADAM_EPS, BETA1, BETA2, STORES, _Flat
+from .mtl import ADAM_EPS, BETA1, BETA2, STORES
+from .net_base import FlatStore, LayerBase
 
 QUIRKS = ("no clip on the softmax outputs (ESCM2 clips, ESMM does not); log_loss has epsilon 1e-4; the loss is the batch mean "
           "of log_loss(pCTR, click) + log_loss(pCTR * pCVR, buy): the cvr tower is trained through the product only; "
@@ -25,16 +26,14 @@ QUIRKS = ("no clip on the softmax outputs (ESCM2 clips, ESMM does not); log_loss
           "hyper_parameters.optimizer.learning_rate")
 
 
-class ESMMLayer:
+class ESMMLayer(LayerBase):
     """esmm/net.py:21-111.  forward(ids [B, num_field, max_len] int64) -> net.py's six outputs; train_step(ids, click [B],
     buy [B], lr) -> (loss, pred [B, 6] = ctr_out | cvr_out | ctcvr_prop)."""
     n_tasks = 2
 
     def __init__(self, sparse_feature_number, sparse_feature_dim, num_field, ctr_layer_sizes, cvr_layer_sizes, max_len=3,
                  device="cuda", kernels=None):
-        from . import ops
-        self.device = torch.device(device)
-        self.k = kernels if kernels is not None else ops     # tests may inject a stand-in backend (host logic only)
+        self._init_runtime(device, kernels)
         self.emb = FieldTable(sparse_feature_number, sparse_feature_dim, num_field, max_len, self.device, self.k)
         K = int(num_field) * int(sparse_feature_dim)
         hidden = [[int(h) for h in (ctr_layer_sizes or [])], [int(h) for h in (cvr_layer_sizes or [])]]
@@ -50,7 +49,7 @@ class ESMMLayer:
             for j in range(1, len(self.sizes[t])):
                 n = "linear_%d" % (self.first[t] + j)
                 entries += [(n + ".weight", (self.sizes[t][j - 1], self.sizes[t][j])), (n + ".bias", (self.sizes[t][j],))]
-        self.flat = _Flat(entries, self.device)
+        self.flat = FlatStore(entries, self.device)
         self._views = {s: {} for s in STORES}
         for s in STORES:
             v, c = self.flat.view[s], 0
@@ -68,11 +67,6 @@ class ESMMLayer:
             self.params[n + ".bias"] = self._views["p"][n + ".bias"]
             w.normal_(0.0, 1.0 / math.sqrt(w.shape[0]))
         self._minus_plus = torch.tensor([[-1.0], [1.0]], dtype=torch.float32, device=self.device)
-        self.training = True
-        self.status = self.k.new_status(self.device)
-        self.ws = self.k.Workspace(self.device)
-        self.step_count = 0
-        self._last = None
 
     # ---------------------------------------------------------------- parameters
     def state_dict(self):
@@ -80,38 +74,11 @@ class ESMMLayer:
         sd.update(self.params)
         return sd
 
-    def parameters(self):
-        return list(self.state_dict().values())
-
-    def set_dict(self, sd):
-        for key, v in sd.items():
-            dst = self.emb.weight if key == "embedding.weight" else self.params[key]
-            dst.copy_(torch.as_tensor(v).to(self.device).reshape(dst.shape))
-
-    set_state_dict = set_dict
-
-    def extra_optimizer_state(self):
-        """checkpoint.py: Adam's moments of every parameter, under the parameter's own name."""
-        out = self.emb.moments()
-        for k in self.params:
-            out["mtl.m." + k] = self._views["m"][k].detach().cpu().numpy().copy()
-            out["mtl.v." + k] = self._views["v"][k].detach().cpu().numpy().copy()
+    def _optimizer_views(self):
+        """Adam's moments of every parameter, under the parameter's own name."""
+        out = self.emb.moment_views()
+        out.update(("mtl.%s.%s" % (s, k), self._views[s][k]) for k in self.params for s in ("m", "v"))
         return out
-
-    def set_extra_optimizer_state(self, st):
-        self.emb.set_moments(st)
-        for k in self.params:
-            for s in ("m", "v"):
-                key = "mtl.%s.%s" % (s, k)
-                if key in st:
-                    dst = self._views[s][k]
-                    dst.copy_(torch.as_tensor(st[key]).to(dst.device).reshape(dst.shape))
-
-    def train(self):
-        self.training = True
-
-    def eval(self):
-        self.training = False
 
     # ---------------------------------------------------------------- forward
     def _cols(self, t):

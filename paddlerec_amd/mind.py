@@ -25,7 +25,8 @@ import math
 import numpy as np
 import torch
 
-from .mtl import ADAM_EPS, BETA1, BETA2, _Flat
+from .mtl import ADAM_EPS, BETA1, BETA2
+from .net_base import FlatStore, LayerBase
 
 QUIRKS = ("the FINAL routing softmax runs over the k_max capsules (net.py:226, axis=1) where the iters - 1 inner rounds run "
           "over the positions: a padded position gets weight exactly 1/k_max on every capsule, not zero, and contributes "
@@ -90,15 +91,13 @@ class MindLoss:
     __float__ = item
 
 
-class Mind_Capsual_Layer:
+class Mind_Capsual_Layer(LayerBase):
     """net.py:116-234.  forward(item_his_emb [B*T, input_units], seq_len [B]) -> (high_capsule [B*K, output_units] after
     relu_layer, W [B, K, T], seq_len); keep: a dict that receives what the backward needs."""
 
     def __init__(self, input_units, output_units, iters=3, maxlen=32, k_max=3, init_std=1.0, batch_size=None, device="cuda",
                  kernels=None):
-        from . import ops
-        self.device = torch.device(device)
-        self.k = kernels if kernels is not None else ops
+        self._init_runtime(device, kernels)
         self.iters, self.input_units, self.output_units = int(iters), int(input_units), int(output_units)
         self.maxlen, self.init_std, self.k_max, self.batch_size = int(maxlen), float(init_std), int(k_max), batch_size
         from ._lib import REC_MIND_MAX_H, REC_MIND_MAX_ITERS, REC_MIND_MAX_K, REC_MIND_MAX_T
@@ -107,15 +106,14 @@ class Mind_Capsual_Layer:
             if not 1 <= v <= hi:
                 raise ValueError("Mind_Capsual_Layer: %s must be in 1..%d, got %d" % (n, hi, v))
         E, H = self.input_units, self.output_units
-        self.flat = _Flat([("bilinear_mapping_matrix", (E, H)), ("relu_layer.weight", (H, H)), ("relu_layer.bias", (H,))],
-                          self.device)
+        self.flat = FlatStore([("bilinear_mapping_matrix", (E, H)), ("relu_layer.weight", (H, H)), ("relu_layer.bias", (H,))],
+                              self.device)
         self.params = self.flat.view["p"]
         self.routing_logits = torch.empty(1, self.k_max, self.maxlen, dtype=torch.float32, device=self.device)
         self.routing_logits.normal_(0.0, self.init_std)                       # trainable=False (net.py:142)
         self.params["bilinear_mapping_matrix"].normal_(0.0, self.init_std)
         lim = math.sqrt(6.0 / (H + H))                                         # nn.Linear: XavierUniform, zero bias [EXT]
         self.params["relu_layer.weight"].uniform_(-lim, lim)
-        self.ws = self.k.Workspace(self.device)
 
     def forward(self, item_his_emb, seq_len, keep=None):
         k, p = self.k, self.params
@@ -142,15 +140,13 @@ class Mind_Capsual_Layer:
         return d_low
 
 
-class MindLayer:
+class MindLayer(LayerBase):
     """net.py:237-318.  forward(hist_item [B, T], seqlen [B]) -> (user_cap [B, K, H], cap_weights [B, K, T]) (eval mode);
     train_step(hist_item, seqlen, labels [B], lr, neg=None) -> (loss: a MindLoss, user_cap, cap_weights)."""
 
     def __init__(self, item_count, embedding_dim, hidden_size, neg_samples=100, maxlen=30, pow_p=1.0, capsual_iters=3,
                  capsual_max_k=3, capsual_init_std=1.0, batch_size=None, device="cuda", kernels=None, seed=12345):
-        from . import ops
-        self.device = torch.device(device)
-        self.k = kernels if kernels is not None else ops     # tests may inject a stand-in backend (host logic only)
+        self._init_runtime(device, kernels, group_status=True)     # the grouping's own status word: see _table_step
         self.item_count, self.embedding_dim, self.hidden_size = int(item_count), int(embedding_dim), int(hidden_size)
         self.neg_samples, self.maxlen, self.pow_p, self.seed = int(neg_samples), int(maxlen), float(pow_p), int(seed)
         if self.item_count < 2 or self.embedding_dim < 1:
@@ -174,13 +170,8 @@ class MindLayer:
         self.prob, log_q = log_uniform_table(N, self.neg_samples)         # host, once (net.py:40-47)
         self.log_q_host = log_q
         self.log_q = log_q.to(self.device)
-        self.training = True
-        self.status = self.k.new_status(self.device)
-        self._group_status = self.k.new_status(self.device)               # the grouping's own word: see _table_step
-        self.ws, self.ws_group = self.capsual_layer.ws, self.k.Workspace(self.device)
-        self.groups = self._pp = None
-        self.step_count = 0
-        self._last = None
+        self.ws = self.capsual_layer.ws                                   # one scratch buffer for both
+        self._pp = None
 
     # ---------------------------------------------------------------- parameters
     def state_dict(self):
@@ -191,43 +182,16 @@ class MindLayer:
                 "capsual_layer.relu_layer.weight": c.params["relu_layer.weight"],
                 "capsual_layer.relu_layer.bias": c.params["relu_layer.bias"]}
 
-    def parameters(self):
-        return list(self.state_dict().values())
-
-    def set_dict(self, sd):
-        mine = self.state_dict()
-        for key, v in sd.items():
-            dst = mine[key]
-            dst.copy_(torch.as_tensor(v).to(self.device).reshape(dst.shape))
-
-    set_state_dict = set_dict
-
     STEPPED = ("item_emb.weight", "capsual_layer.bilinear_mapping_matrix", "capsual_layer.relu_layer.weight",
                "capsual_layer.relu_layer.bias")
 
-    def _moment_views(self, s):
-        v = self.capsual_layer.flat.view[s]
-        return {"item_emb.weight": self.emb_m if s == "m" else self.emb_v,
-                "capsual_layer.bilinear_mapping_matrix": v["bilinear_mapping_matrix"],
-                "capsual_layer.relu_layer.weight": v["relu_layer.weight"], "capsual_layer.relu_layer.bias": v["relu_layer.bias"]}
-
-    def extra_optimizer_state(self):
-        """checkpoint.py: Adam's moments of every stepped parameter, under the parameter's own name."""
-        return {"mtl.%s.%s" % (s, k): v.detach().cpu().numpy().copy() for s in ("m", "v")
-                for k, v in self._moment_views(s).items()}
-
-    def set_extra_optimizer_state(self, st):
-        for s in ("m", "v"):
-            for k, dst in self._moment_views(s).items():
-                key = "mtl.%s.%s" % (s, k)
-                if key in st:
-                    dst.copy_(torch.as_tensor(st[key]).to(dst.device).reshape(dst.shape))
-
-    def train(self):
-        self.training = True
-
-    def eval(self):
-        self.training = False
+    def _optimizer_views(self):
+        """Adam's moments of every stepped parameter (STEPPED), under the parameter's own name."""
+        out = {}
+        for s, t in (("m", self.emb_m), ("v", self.emb_v)):
+            out["mtl.%s.item_emb.weight" % s] = t
+            out.update(("mtl.%s.capsual_layer.%s" % (s, k), v) for k, v in self.capsual_layer.flat.view[s].items())
+        return out
 
     # ---------------------------------------------------------------- negatives
     def sample_negatives(self, step):
@@ -307,12 +271,10 @@ class MindLayer:
         k = self.k
         pad = lambda ids: torch.where(ids == 0, torch.full_like(ids, -1), ids)
         rows = torch.cat([pad(hist_item.reshape(-1)), pad(labels), labels, neg])
-        if self.groups is None or self.groups.n != rows.numel():
-            self.groups = k.IdGroups(rows.numel(), self.device)
-        k.ids_group(rows, self.item_count, None, self.ws_group, None, self._group_status, self.groups)
+        groups = self._grouped("emb", rows, self.item_count, None, self._group_status)
         E = self.embedding_dim
-        self._pp = k.segment_partials(self.groups, G, E, out=self._pp)
-        k.adam_rows_all(self.groups, G, 1, self.emb, self.emb_m, self.emb_v, self.step_count, lr, BETA1, BETA2, ADAM_EPS,
+        self._pp = k.segment_partials(groups, G, E, out=self._pp)
+        k.adam_rows_all(groups, G, 1, self.emb, self.emb_m, self.emb_v, self.step_count, lr, BETA1, BETA2, ADAM_EPS,
                         partials=self._pp)
 
     def last_gradients(self):

@@ -30,36 +30,15 @@ How it runs, with the same result as the reference:
     (sum over tasks of the batch mean) is only taken, with torch, when something reads it.  A subclass may put another
     head in its place (_head, _loss) and ask for the features' gradient (level0_dx): escm2.py does both.
 The train step is eager (no graph capture); the only torch work on its path is allocation."""
-import math
-
 import torch
 
-from . import ops
-from .din import NUM_THRESHOLDS
+from .net_base import FlatStore, LayerBase, auc_metrics, auc_update
 
 BETA1, BETA2, ADAM_EPS = 0.9, 0.999, 1e-8
 STORES = ("p", "g", "m", "v")
 
 
-def _pad4(n):
-    return (n + 3) // 4 * 4
-
-
-class _Flat:
-    """Named tensors in one flat float32 buffer, four times: values, gradients, Adam m and v (one rec_adam_dense)."""
-
-    def __init__(self, entries, device):
-        total = sum(_pad4(math.prod(sh)) for _, sh in entries)
-        self.flat = {s: torch.zeros(total, dtype=torch.float32, device=device) for s in STORES}
-        self.view, o = {s: {} for s in STORES}, 0
-        for name, sh in entries:
-            n = math.prod(sh)
-            for s in STORES:
-                self.view[s][name] = self.flat[s][o:o + n].view(sh)
-            o += _pad4(n)
-
-
-class _Image(_Flat):
+class _Image(FlatStore):
     """The packed image of the Linears that read one input: cols = [(name, width)] in column order."""
 
     def __init__(self, K, cols, device):
@@ -96,12 +75,11 @@ class LazyLoss:
     __float__ = item
 
 
-class MtlLayer:
+class MtlLayer(LayerBase):
     """forward(x [B, F]) -> [pred_t [B, 2]] per task; train_step(x, label [B, T] float32, lr) -> (loss, pred [B, 2T])."""
 
     def __init__(self, plan, device="cuda", kernels=None):
-        self.device = torch.device(device)
-        self.k = kernels if kernels is not None else ops     # tests may inject a stand-in backend (host logic only)
+        self._init_runtime(device, kernels)
         self.plan, self.tasks = plan, int(plan["tasks"])
         shape = {n: (int(i), int(o)) for n, i, o, _, _ in plan["params"]}
         self.levels, self._copies = [], {}                   # _copies: name -> [(image, column block)] in slot order
@@ -137,7 +115,7 @@ class MtlLayer:
         for t in range(self.tasks):
             for n in ("tower_%d" % t, "tower_out_%d" % t):
                 towers += [(n + ".weight", shape[n]), (n + ".bias", (shape[n][1],))]
-        self.tail = _Flat(towers, self.device)
+        self.tail = FlatStore(towers, self.device)
         # the reference's separate tensors: the first slot's column range, a tower's entry, or a tensor of its own
         self.params, self._views = {}, {s: {} for s in STORES}
         for n, i, o, wv, bv in plan["params"]:
@@ -164,11 +142,6 @@ class MtlLayer:
                 self.aliases[a + suffix] = n + suffix
         self._sync_copies(("p",))
         self._minus_plus = torch.tensor([[-1.0], [1.0]], dtype=torch.float32, device=self.device)
-        self.training = True
-        self.status = self.k.new_status(self.device)
-        self.ws = self.k.Workspace(self.device)
-        self.step_count = 0
-        self._last = None
         self.level0_dx = False      # True: train_step also runs level 0's dX GEMM and keeps it as self._last["dX"]
 
     # ---------------------------------------------------------------- parameters
@@ -191,42 +164,23 @@ class MtlLayer:
         return sd
 
     def parameters(self):
-        return list(self.params.values())
+        return list(self.params.values())       # every Linear once: state_dict shows an aliased one twice
 
     def set_dict(self, sd):
-        for key, v in sd.items():
-            dst = self.params[self.aliases.get(key, key)]
-            dst.copy_(torch.as_tensor(v).to(self.device).reshape(dst.shape))
+        super().set_dict(sd)                    # an alias key: state_dict holds the same tensor under it
         self._sync_copies(("p",))
-
-    set_state_dict = set_dict
 
     def trainable(self):
         """The state_dict keys the optimizer moves (every Linear forward() calls)."""
         return [k for k in self.params if k in self._views["g"]]
 
-    def extra_optimizer_state(self):
-        """checkpoint.py: Adam's moments of every trainable parameter, under the parameter's own name."""
-        out = {}
-        for k in self.trainable():
-            out["mtl.m." + k] = self._views["m"][k].detach().cpu().numpy().copy()
-            out["mtl.v." + k] = self._views["v"][k].detach().cpu().numpy().copy()
-        return out
+    def _optimizer_views(self):
+        """Adam's moments of every trainable parameter, under the parameter's own name."""
+        return {"mtl.%s.%s" % (s, k): self._views[s][k] for k in self.trainable() for s in ("m", "v")}
 
     def set_extra_optimizer_state(self, st):
-        for k in self.trainable():
-            for s in ("m", "v"):
-                key = "mtl.%s.%s" % (s, k)
-                if key in st:
-                    dst = self._views[s][k]
-                    dst.copy_(torch.as_tensor(st[key]).to(dst.device).reshape(dst.shape))
+        super().set_extra_optimizer_state(st)
         self._sync_copies(("m", "v"))
-
-    def train(self):
-        self.training = True
-
-    def eval(self):
-        self.training = False
 
     # ---------------------------------------------------------------- forward
     def _run(self, x, keep=None):
@@ -397,14 +351,11 @@ class MtlDygraphModel:
         return x, torch.cat(labels, 1)
 
     def create_metrics(self, device="cuda"):
-        pair = lambda: (torch.zeros(NUM_THRESHOLDS + 1, dtype=torch.int64, device=device),
-                        torch.zeros(NUM_THRESHOLDS + 1, dtype=torch.int64, device=device))
-        return [pair(), pair()], ["auc_income", "auc_marital"]
+        return auc_metrics(device, ("auc_income", "auc_marital"))
 
     def _auc(self, dy_model, metrics_list, pred, label):
         for t, m in enumerate(metrics_list[:2]):               # column 1 of task t's prediction
-            dy_model.k.auc_histogram(pred[:, 2 * t + 1].contiguous(), label[:, t].to(torch.int64).contiguous(), m[0], m[1],
-                                     NUM_THRESHOLDS)
+            auc_update(dy_model.k, m, pred[:, 2 * t + 1], label[:, t])
 
     def _check(self, dy_model):
         if dy_model.tasks != 2:

@@ -19,6 +19,8 @@ import os
 import numpy as np
 import torch
 
+from .net_base import LayerBase
+
 MODES = ("NCF_NeuMF", "NCF_GMF", "NCF_MLP")
 QUIRKS = ("prediction.in_features is written as layers[2] (NeuMF) or layers[3] (GMF, MLP) in net.py, which equals the true "
           "width only for numbers like the shipped ones; the mirror computes the true width and refuses a configuration for "
@@ -46,13 +48,12 @@ def prediction_width(mode, mf_dim, layers):
     return true
 
 
-class NCFLayer:
+class NCFLayer(LayerBase):
     """net.py:22-241.  forward(users, items) -> prediction [B, 1];  train_step(users, items, labels, lr) -> loss [1]."""
 
     def __init__(self, num_users, num_items, mf_dim, layers, mode="NCF_NeuMF", device="cuda", kernels=None):
-        from . import ops
-        self.device = torch.device(device)
-        self.k = k = kernels if kernels is not None else ops
+        self._init_runtime(device, kernels, group_status=True)
+        k = self.k
         self.mode, self.num_users, self.num_items = mode, int(num_users), int(num_items)
         self.layers = [int(x) for x in layers]
         self.pred_width = prediction_width(mode, mf_dim, self.layers)
@@ -76,14 +77,7 @@ class NCFLayer:
         self.flat = {s: torch.zeros(self.P, **f32) for s in ("p", "g", "m", "v")}
         self.fused = k.ncf_fused_eligible(self.desc) and os.environ.get("REC_NCF_FUSED", "1") != "0"
         self._init()
-        self.training = True
-        self.status = k.new_status(self.device)
-        self._group_status = k.new_status(self.device)
-        self.ws = k.Workspace(self.device)
-        self.ws_group = k.Workspace(self.device)
-        self._scratch, self._groups, self._buf = {}, {}, {}
-        self._last = None
-        self.step_count = 0
+        self._scratch, self._buf = {}, {}
 
     # ---------------------------------------------------------------- parameters
     def _views(self, store):
@@ -121,39 +115,15 @@ class NCFLayer:
     def state_dict(self):
         return self._views("p")
 
-    def parameters(self):
-        return list(self.state_dict().values())
-
     def moments(self):
         return self._views("m"), self._views("v")
 
-    def set_dict(self, sd):
-        mine = self.state_dict()
-        for key, v in sd.items():
-            dst = mine[key]
-            dst.copy_(torch.as_tensor(np.asarray(v) if not torch.is_tensor(v) else v).to(self.device).reshape(dst.shape))
+    def load_state_dict(self, sd):
+        self.set_dict(sd)
 
-    set_state_dict = load_state_dict = set_dict
-
-    def extra_optimizer_state(self):
-        """checkpoint.py: Adam's moments of every parameter, under the parameter's own name."""
-        out = {}
-        for s in ("m", "v"):
-            out.update(("ncf.%s.%s" % (s, k), v.detach().cpu().numpy().copy()) for k, v in self._views(s).items())
-        return out
-
-    def set_extra_optimizer_state(self, st):
-        for s in ("m", "v"):
-            for k, dst in self._views(s).items():
-                key = "ncf.%s.%s" % (s, k)
-                if key in st:
-                    dst.copy_(torch.as_tensor(st[key]).to(dst.device).reshape(dst.shape))
-
-    def train(self):
-        self.training = True
-
-    def eval(self):
-        self.training = False
+    def _optimizer_views(self):
+        """Adam's moments of every parameter, under the parameter's own name."""
+        return {"ncf.%s.%s" % (s, k): v for s in ("m", "v") for k, v in self._views(s).items()}
 
     # ---------------------------------------------------------------- forward
     def _feeds(self, users, items, labels=None):
@@ -211,13 +181,6 @@ class NCFLayer:
     __call__ = forward
 
     # ---------------------------------------------------------------- training
-    def _group(self, side, ids, rows):
-        g = self._groups.get(side)
-        if g is None or g.n != ids.numel():
-            g = self._groups[side] = self.k.IdGroups(ids.numel(), self.device)
-        self.k.ids_group(ids, rows, None, self.ws_group, None, self._group_status, g)
-        return g
-
     def train_step(self, users, items, labels, lr=0.001, mean_over=0):
         """dygraph_model.py:50-80: forward, log loss, backward and Adam on every parameter -> loss [1]."""
         k, T, fl = self.k, self.packed, self.flat
@@ -248,7 +211,8 @@ class NCFLayer:
             pred = pred.view(-1)
         k.adam_dense(fl["p"], fl["m"], fl["v"], fl["g"], self.step_count, lr=lr)
         for side, ids, rows, grad in (("user", u, self.num_users, gu), ("item", i, self.num_items, gi)):
-            k.adam_rows_all(self._group(side, ids, rows), grad, 1, T["p"][side], T["m"][side], T["v"][side], self.step_count, lr=lr)
+            groups = self._grouped(side, ids, rows, None, self._group_status)
+            k.adam_rows_all(groups, grad, 1, T["p"][side], T["m"][side], T["v"][side], self.step_count, lr=lr)
         self._last = dict(u=u, i=i, gu=gu, gi=gi, pred=pred)
         return loss
 

@@ -13,9 +13,7 @@ on the instance (paddlerec_amd.trainer probes the class).  The base defines neit
 """
 import torch
 
-from . import ops
-
-NUM_THRESHOLDS = 4095  # paddle.metric.Auc default [EXT]
+from .net_base import NUM_THRESHOLDS, LayerBase, auc_metrics  # noqa: F401 (re-exported)
 
 
 class _OnSide:
@@ -43,30 +41,15 @@ def _round_up(x, m):
 _PARTIALS = ("_pp", "_pp1")     # the attributes that keep a step's segment_partials outputs, one per table
 
 
-class SlotLayerBase:
+class SlotLayerBase(LayerBase):
     """Parameters live in `self.dense` (a _FlatParams) and in the tables `state_dict` names; `self.k` is the operator
     backend."""
 
     def _init_runtime(self, device, kernels):
-        self.device = torch.device(device)
-        self.k = kernels if kernels is not None else ops     # tests may inject a stand-in backend (host logic only)
-        self.ws = self.k.Workspace(self.device)
-        self.ws_group = self.k.Workspace(self.device)
-        self.status = self.k.new_status(self.device)
-        self.step_count = 0
+        super()._init_runtime(device, kernels)
         self.sparse_state = None
         self._side = None
         self._groups = None
-
-    # -- parameters under the reference's state_dict keys ---------------------------------------
-    def set_dict(self, sd):
-        cur = self.state_dict()
-        for k, v in sd.items():
-            dst = cur[k]
-            dst.copy_(torch.as_tensor(v).to(dst.device).reshape(dst.shape))
-
-    def parameters(self):
-        return list(self.state_dict().values())
 
     def grad_dict(self):
         """Dense gradients of the last train_step under the reference's parameter names."""
@@ -178,13 +161,6 @@ def slot_feeds(batch_data, config, device):
     sparse = [torch.as_tensor(b).to(torch.int64).reshape(-1, 1).to(device) for b in batch_data[:-1]]
     dense = torch.as_tensor(batch_data[-1]).to(torch.float32).reshape(-1, dn).to(device)
     return sparse[0], sparse[1:], dense
-
-
-def auc_metrics(device):
-    """create_metrics: paddle.metric.Auc("ROC") = the two int64 bucket arrays of rec_auc_histogram, on the device."""
-    stats = (torch.zeros(NUM_THRESHOLDS + 1, dtype=torch.int64, device=device),
-             torch.zeros(NUM_THRESHOLDS + 1, dtype=torch.int64, device=device))
-    return [stats], ["auc"]
 
 
 class SlotDygraphModel:

@@ -24,7 +24,8 @@ import math
 import numpy as np
 import torch
 
-from .mtl import ADAM_EPS, BETA1, _Flat
+from .mtl import ADAM_EPS, BETA1
+from .net_base import FlatStore, LayerBase
 
 BETA2 = 0.98                                     # dygraph_model.py:58-63
 LN_EPS = 1e-8
@@ -68,16 +69,14 @@ class TiSASLoss:
     __float__ = item
 
 
-class TiSASRecLayer:
+class TiSASRecLayer(LayerBase):
     """net.py:167-309.  forward(log_seqs [B, L], time_matrices [B, L, L], item_indices=None, pos_seqs=None, neg_seqs=None)
     -> logits [B, I] with item_indices, else (pos_logits, neg_logits) [B, L];
     train_step(log_seqs, time_matrices, pos_seqs, neg_seqs, lr) -> (loss: a TiSASLoss, log_feats [B, L, D])."""
 
     def __init__(self, user_num, item_num, hidden_units, maxlen, time_span, num_blocks, num_heads, dropout_rate=0.2,
                  device="cuda", kernels=None, dropout_seed=12345):
-        from . import ops
-        self.device = torch.device(device)
-        self.k = kernels if kernels is not None else ops     # tests may inject a stand-in backend (host logic only)
+        self._init_runtime(device, kernels, group_status=True)
         self.user_num, self.item_num = int(user_num), int(item_num)
         D, H = int(hidden_units), int(num_heads)
         self.hidden_units, self.maxlen, self.time_span = D, int(maxlen), int(time_span)
@@ -112,7 +111,7 @@ class TiSASRecLayer:
             entries += [("forward_layernorms.%d.weight" % n, (D,)), ("forward_layernorms.%d.bias" % n, (D,))]
             for c in ("conv1", "conv2"):                     # kept as the [C_in, C_out] image; see _conv_names
                 entries += [("forward_layers.%d.%s.weight" % (n, c), (D, D)), ("forward_layers.%d.%s.bias" % (n, c), (D,))]
-        self.flat = _Flat(entries, self.device)
+        self.flat = FlatStore(entries, self.device)
         self._conv_names = {n for n, _ in entries if ".conv" in n and n.endswith(".weight")}
         self.params = self.flat.view["p"]
         for name, sh in entries:
@@ -121,14 +120,8 @@ class TiSASRecLayer:
                 t.fill_(1.0 if name.endswith(".weight") else 0.0)
             elif name.endswith(".weight"):
                 xavier(t, sh[0], sh[1])                      # XavierUniform; every bias starts at zero [EXT]
-        self.training = True
-        self.status = self.k.new_status(self.device)
-        self._group_status = self.k.new_status(self.device)
-        self.ws, self.ws_group = self.k.Workspace(self.device), self.k.Workspace(self.device)
-        self.groups = self._pp = None
+        self._pp = None
         self._scratch = {}
-        self.step_count = 0
-        self._last = None
         self.streams_per_step = len(SITES) + 3 * self.num_blocks
 
     # ---------------------------------------------------------------- parameters
@@ -142,33 +135,9 @@ class TiSASRecLayer:
     def state_dict(self):
         return self._shown("p")
 
-    def parameters(self):
-        return list(self.state_dict().values())
-
-    def set_dict(self, sd):
-        mine = self.state_dict()
-        for key, v in sd.items():
-            dst = mine[key]
-            dst.copy_(torch.as_tensor(np.asarray(v) if not torch.is_tensor(v) else v).to(self.device).reshape(dst.shape))
-
-    set_state_dict = set_dict
-
-    def extra_optimizer_state(self):
-        """checkpoint.py: Adam's moments of every parameter, under the parameter's own name."""
-        return {"mtl.%s.%s" % (s, k): v.detach().cpu().numpy().copy() for s in ("m", "v") for k, v in self._shown(s).items()}
-
-    def set_extra_optimizer_state(self, st):
-        for s in ("m", "v"):
-            for k, dst in self._shown(s).items():
-                key = "mtl.%s.%s" % (s, k)
-                if key in st:
-                    dst.copy_(torch.as_tensor(st[key]).to(dst.device).reshape(dst.shape))
-
-    def train(self):
-        self.training = True
-
-    def eval(self):
-        self.training = False
+    def _optimizer_views(self):
+        """Adam's moments of every parameter, under the parameter's own name."""
+        return {"mtl.%s.%s" % (s, k): v for s in ("m", "v") for k, v in self._shown(s).items()}
 
     # ---------------------------------------------------------------- dropout sites
     def dropout_streams(self, step):
@@ -302,12 +271,10 @@ class TiSASRecLayer:
         k.adam_dense(fl["p"], fl["m"], fl["v"], fl["g"], self.step_count, lr, BETA1, BETA2, ADAM_EPS)
         rows = torch.cat([ids, pos, neg])
         self._last = dict(G=G, rows=rows)
-        if self.groups is None or self.groups.n != rows.numel():
-            self.groups = k.IdGroups(rows.numel(), self.device)
         # every lookup went through the padding Embedding: id 0 takes no gradient
-        k.ids_group(rows, self.item_num + 1, 0, self.ws_group, None, self._group_status, self.groups)
-        self._pp = k.segment_partials(self.groups, G, D, out=self._pp)
-        k.adam_rows_all(self.groups, G, 1, self.emb, self.emb_m, self.emb_v, self.step_count, lr, BETA1, BETA2, ADAM_EPS,
+        groups = self._grouped("emb", rows, self.item_num + 1, 0, self._group_status)
+        self._pp = k.segment_partials(groups, G, D, out=self._pp)
+        k.adam_rows_all(groups, G, 1, self.emb, self.emb_m, self.emb_v, self.step_count, lr, BETA1, BETA2, ADAM_EPS,
                         partials=self._pp)
         return TiSASLoss(loss2), feats.view(B, L, D)
 

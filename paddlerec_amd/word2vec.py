@@ -14,6 +14,8 @@ Names are the reference's: embedding.weight, embedding_w.weight, embedding_b.wei
 import numpy as np
 import torch
 
+from .net_base import LayerBase
+
 QUIRKS = ("the loss is binary_cross_entropy(sigmoid(true), 1) + binary_cross_entropy(sigmoid(neg), 0), each with its default "
           "MEAN reduction (dygraph_model.py:60-66): the true term is averaged over B and the negative term over B * neg — a "
           "mean of means, not a mean over B (1 + neg) — and the trailing paddle.mean of a scalar changes nothing; it is two "
@@ -30,15 +32,13 @@ QUIRKS = ("the loss is binary_cross_entropy(sigmoid(true), 1) + binary_cross_ent
           "':'; only embedding.weight matters to infer; the learning-rate decay keys are read by the static model only")
 
 
-class Word2VecLayer:
+class Word2VecLayer(LayerBase):
     """net.py:21-81.  train_step(in_ids [B], target_ids [B, 1 + neg], lr) -> (loss [1], true_logits [B], neg_logits [B, neg])."""
 
     def __init__(self, sparse_feature_number, emb_dim, neg_num, emb_name="emb", emb_w_name="emb_w", emb_b_name="emb_b",
                  device="cuda", kernels=None):
-        from . import ops
         from ._lib import REC_W2V_MAX_DIM, REC_W2V_MAX_NEG
-        self.device = torch.device(device)
-        self.k = kernels if kernels is not None else ops     # tests may inject a stand-in backend (host logic only)
+        self._init_runtime(device, kernels, group_status=True)   # the groupings' own word (the forward has flagged already)
         self.sparse_feature_number, self.emb_dim, self.neg_num = int(sparse_feature_number), int(emb_dim), int(neg_num)
         self.emb_name, self.emb_w_name, self.emb_b_name = emb_name, emb_w_name, emb_b_name
         if self.sparse_feature_number < 1 or not 1 <= self.emb_dim <= REC_W2V_MAX_DIM:
@@ -51,35 +51,12 @@ class Word2VecLayer:
         self.emb = torch.empty(V, D, **f32).uniform_(-init_width, init_width)
         self.emb_w = torch.zeros(V, D, **f32)                                  # net.py:48, :56: Constant(0.0)
         self.emb_b = torch.zeros(V, 1, **f32)
-        self.status = self.k.new_status(self.device)
-        self._group_status = self.k.new_status(self.device)      # the groupings' own word (the forward has flagged already)
-        self.ws_group = self.k.Workspace(self.device)
-        self.groups_t = self.groups_in = self._pp = None
+        self._pp = None
         self.record_gradients = False            # True: every step also leaves the merged target-row gradients
-        self.training = True
-        self.step_count = 0
-        self._last = None
 
     # ---------------------------------------------------------------- parameters
     def state_dict(self):
         return {"embedding.weight": self.emb, "embedding_w.weight": self.emb_w, "embedding_b.weight": self.emb_b}
-
-    def parameters(self):
-        return list(self.state_dict().values())
-
-    def set_dict(self, sd):
-        mine = self.state_dict()
-        for key, v in sd.items():
-            dst = mine[key]
-            dst.copy_(torch.as_tensor(v).to(self.device).reshape(dst.shape))
-
-    set_state_dict = set_dict
-
-    def train(self):
-        self.training = True
-
-    def eval(self):
-        self.training = False
 
     # ---------------------------------------------------------------- forward / training
     def _check(self, in_ids, target_ids):
@@ -113,17 +90,15 @@ class Word2VecLayer:
             k.raise_on_status(self.status, "word2vec")
         self.step_count += 1
         n = target_ids.numel()
-        if self.groups_t is None or self.groups_t.n != n:
-            self.groups_t, self.groups_in = k.IdGroups(n, self.device), k.IdGroups(B, self.device)
-        k.ids_group(target_ids.reshape(-1), V, None, self.ws_group, None, self._group_status, self.groups_t)
+        groups_t = self._grouped("target", target_ids.reshape(-1), V, None, self._group_status)
         dw = db = None
         if self.record_gradients:
             dw = torch.zeros(n, D, dtype=torch.float32, device=self.device)
             db = torch.zeros(n, dtype=torch.float32, device=self.device)
-        k.w2v_target_update(self.groups_t, g, in_ids, self.emb, self.emb_w, self.emb_b, lr, dw, db)     # reads the OLD emb
-        k.ids_group(in_ids, V, None, self.ws_group, None, self._group_status, self.groups_in)
-        self._pp = k.segment_partials(self.groups_in, d_in, D, out=self._pp)
-        k.sparse_sgd_rows(self.groups_in, d_in, self.emb, lr, partials=self._pp)
+        k.w2v_target_update(groups_t, g, in_ids, self.emb, self.emb_w, self.emb_b, lr, dw, db)     # reads the OLD emb
+        groups_in = self._grouped("in", in_ids, V, None, self._group_status)
+        self._pp = k.segment_partials(groups_in, d_in, D, out=self._pp)
+        k.sparse_sgd_rows(groups_in, d_in, self.emb, lr, partials=self._pp)
         self._last = dict(in_ids=in_ids, d_in=d_in, dw=dw, db=db, g=g)
         return loss, true_logits, neg_logits
 
@@ -133,7 +108,7 @@ class Word2VecLayer:
         last = self._last
         if last is None or last["dw"] is None:
             raise RuntimeError("set record_gradients = True before the train_step whose gradients are wanted")
-        sp, uniq, offs = self.groups_t.host()
+        sp, uniq, offs = self._id_groups["target"].host()
         rows = torch.as_tensor(np.asarray(uniq), dtype=torch.int64, device=self.device)
         U = rows.numel()
         ok = (last["in_ids"] >= 0) & (last["in_ids"] < self.sparse_feature_number)
@@ -142,14 +117,12 @@ class Word2VecLayer:
                 "embedding_b.weight": torch.zeros_like(self.emb_b).index_add_(0, rows, last["db"][:U].view(-1, 1))}
 
 
-class Word2VecInferLayer:
+class Word2VecInferLayer(LayerBase):
     """net.py:84-110.  forward(analogy_a, analogy_b, analogy_c [B] or [B, 1], k=4) -> (values [B, k], pred_idx [B, k]); the
     reference's all_label argument is the whole vocabulary in order and is not needed."""
 
     def __init__(self, sparse_feature_number, emb_dim, emb_name="emb", device="cuda", kernels=None, table=None):
-        from . import ops
-        self.device = torch.device(device)
-        self.k = kernels if kernels is not None else ops
+        self._init_runtime(device, kernels)
         self.sparse_feature_number, self.emb_dim, self.emb_name = int(sparse_feature_number), int(emb_dim), emb_name
         if table is not None:
             self.emb = table                                   # share a trained layer's table
@@ -157,19 +130,13 @@ class Word2VecInferLayer:
             init_width = 0.5 / self.emb_dim
             self.emb = torch.empty(self.sparse_feature_number, self.emb_dim, dtype=torch.float32,
                                    device=self.device).uniform_(-init_width, init_width)
-        self.status = self.k.new_status(self.device)
 
     def state_dict(self):
         return {"embedding.weight": self.emb}
 
     def set_dict(self, sd):
-        if "embedding.weight" in sd:                           # infer.py loads a training checkpoint: the other keys are not ours
-            self.emb.copy_(torch.as_tensor(sd["embedding.weight"]).to(self.device).reshape(self.emb.shape))
-
-    set_state_dict = set_dict
-
-    def eval(self):
-        pass
+        mine = self.state_dict()                               # infer.py loads a training checkpoint: the other keys are not ours
+        super().set_dict({key: v for key, v in sd.items() if key in mine})
 
     def forward(self, analogy_a, analogy_b, analogy_c, all_label=None, k=4):
         a, b, c = (t.reshape(-1).to(torch.int64).contiguous() for t in (analogy_a, analogy_b, analogy_c))
