@@ -2365,6 +2365,52 @@ int rec_ncf_gather_bwd(int32_t mf_dim, int32_t n_fc, const int32_t* widths, int6
                        const float* d_mlp_in, int64_t ld_dmlp_in, float* g_user, int64_t ld_gu, float* g_item, int64_t ld_gi,
                        void* stream);
 
+/* ----------------------------------------------------------------------------------------
+ * DSSM (models/match/dssm): the two-tower semantic-matching net (csrc/dssm_ops.hip).  float32; no float atomics; every sum
+ * has a fixed order and nothing depends on the order in which blocks run, so a rerun is bit-identical.  Arguments are checked
+ * on the host before any launch (REC_EINVAL, the entry and the argument named in rec_last_error()); a call with no rows
+ * returns REC_OK without a launch after those checks.  No entry takes a workspace: every intermediate is a named buffer.
+ *
+ * A tower input of `rows` multi-hot rows over in_dim letter trigrams is CSR: cols [nnz] int64 (ascending within a row), vals
+ * [nnz] float32, lod [rows + 1] int64 (lod[r] .. lod[r + 1] are row r's entries; values are clamped to 0 .. nnz).
+ *
+ * rec_dssm_lod_rows: row_of[j] = the row that holds entry j, int32 [nnz] (what the backward reads; a reader may supply it).
+ * rec_dssm_sparse_linear_fwd: Y[r, :] = act(bias + sum_j vals[j] * W[cols[j], :]) over row r's entries in stored order; W
+ *   [in_dim, n] row-major (ld_w), act = ReLU when relu != 0.  A row without entries gives act(bias).  A column outside
+ *   [0, in_dim) sets REC_FLAG_INDEX_OOB in *status (may be NULL) and is skipped.  float4 lanes when n, ld_w and ld_y are
+ *   multiples of 4 and W, bias and Y are 16-byte aligned, one float per lane otherwise.
+ * rec_dssm_sparse_linear_bwd: dW[c, :] = sum vals[j] * dY[row_of[j], :] over the entries j with cols[j] == c in ascending j,
+ *   for EVERY c of [0, in_dim): a column no row holds gets zeros, so no memset precedes the call.  The entries grouped by
+ *   column are rec_ids_group's outputs for ids = cols, num_rows = in_dim (sorted_pos [nnz]: entry indices, stable; uniq_rows,
+ *   seg_offset, n_uniq as documented there; out-of-range columns were dropped there).  One block of REC_DSSM_BWD_WAVES waves
+ *   per column: wave w sums the w-th part of the column's entries (ceil(len / waves) each, ascending), the parts are folded in
+ *   ascending w.  n <= REC_DSSM_MAX_WIDTH (the parts' LDS).  dY is the gradient already masked by the layer's ReLU; there is
+ *   no dX (the inputs are data) and db is rec_colsum(dY).
+ * rec_dssm_head_step: cosine, softmax, loss and their backward in one launch plus a one-wave fold.  q [batch, n] (ld_q);
+ *   d [(1 + neg) * batch, n] (ld_d) field-major: the positives' rows first, then each negative's.  cos[b, k] = w12 /
+ *   sqrt(max(w1 * w2, 1e-16)) (Paddle's cosine_similarity, eps 1e-8) -> cos [batch, 1 + neg]; hit_prob[b] =
+ *   softmax_k(cos[b, :])[0] -> [batch]; loss_terms[b] = -log(hit_prob[b]) -> [batch]; loss [1] = the mean of the first M =
+ *   min(batch, slice_end) terms in a fixed order; dq [batch, n] (ld_dq) and dd [(1 + neg) * batch, n] (ld_dd) = d loss, zeros
+ *   for rows b >= M.  Where w1 * w2 < 1e-16 the clamped branch holds in value and gradient (d cos / d x = y / 1e-8).
+ *   relu_mask != 0: q and d are ReLU outputs, and dq / dd are zeroed where they are not positive.  neg = 0 is legal;
+ *   1 + neg <= REC_DSSM_MAX_DOCS; slice_end >= 1.
+ * rec_dssm_cos: cos[b] of q [batch, n] against d [batch, n] alone (inference).
+ * ---------------------------------------------------------------------------------------- */
+#define REC_DSSM_MAX_DOCS 64
+#define REC_DSSM_MAX_WIDTH 2048
+#define REC_DSSM_BWD_WAVES 8
+int rec_dssm_lod_rows(int64_t rows, int64_t nnz, const int64_t* lod, int32_t* row_of, void* stream);
+int rec_dssm_sparse_linear_fwd(int64_t rows, int64_t nnz, int64_t in_dim, int32_t n, int32_t relu, const int64_t* cols,
+                               const float* vals, const int64_t* lod, const float* W, int64_t ld_w, const float* bias, float* Y,
+                               int64_t ld_y, int32_t* status, void* stream);
+int rec_dssm_sparse_linear_bwd(int64_t rows, int64_t nnz, int64_t in_dim, int32_t n, const float* vals, const int32_t* row_of,
+                               const int32_t* sorted_pos, const int64_t* uniq_rows, const int32_t* seg_offset,
+                               const int32_t* n_uniq, const float* dY, int64_t ld_dy, float* dW, int64_t ld_dw, void* stream);
+int rec_dssm_head_step(int64_t batch, int32_t neg, int32_t n, int64_t slice_end, int32_t relu_mask, const float* q, int64_t ld_q,
+                       const float* d, int64_t ld_d, float* cos, float* hit_prob, float* loss_terms, float* loss, float* dq,
+                       int64_t ld_dq, float* dd, int64_t ld_dd, void* stream);
+int rec_dssm_cos(int64_t batch, int32_t n, const float* q, int64_t ld_q, const float* d, int64_t ld_d, float* cos, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4334,3 +4334,112 @@ def ncf_gather_bwd(desc, users, items, user_table, item_table, d_pred_in, d_mlp_
                                    _p(d_pred_in), ldp, _p(d_mlp_in), ldm, _p(g_user), _rows_view(g_user, "g_user"), _p(g_item),
                                    _rows_view(g_item, "g_item"), _stream()), "rec_ncf_gather_bwd")
     return g_user, g_item
+
+
+# ------------------------------------------------------------------ DSSM (models/match/dssm, csrc/dssm_ops.hip)
+DSSM_MAX_DOCS, DSSM_MAX_WIDTH = _lib.REC_DSSM_MAX_DOCS, _lib.REC_DSSM_MAX_WIDTH
+
+
+def _dssm_csr(cols, vals, lod, what):
+    """A tower input in CSR (include/recengine.h): cols int64 [nnz], vals float32 [nnz], lod int64 [rows + 1] -> (rows, nnz)."""
+    _chk(cols, torch.int64, "cols")
+    _chk(vals, torch.float32, "vals")
+    _chk(lod, torch.int64, "lod")
+    if cols.dim() != 1 or vals.dim() != 1 or lod.dim() != 1 or cols.numel() != vals.numel() or lod.numel() < 1:
+        raise RecError("%s: cols and vals must be [nnz] and lod [rows + 1]" % what)
+    return lod.numel() - 1, cols.numel()
+
+
+def dssm_lod_rows(lod, nnz, out=None):
+    """rec_dssm_lod_rows: row_of [nnz] int32, the row of every CSR entry."""
+    _chk(lod, torch.int64, "lod")
+    if lod.dim() != 1 or lod.numel() < 1:
+        raise RecError("dssm_lod_rows: lod must be [rows + 1]")
+    if out is None:
+        out = torch.empty(max(int(nnz), 1), dtype=torch.int32, device=lod.device)
+    _chk(out, torch.int32, "row_of")
+    if out.numel() < nnz:
+        raise RecError("dssm_lod_rows: row_of shorter than nnz")
+    check(lib().rec_dssm_lod_rows(lod.numel() - 1, int(nnz), _p(lod), _p(out), _stream()), "rec_dssm_lod_rows")
+    return out
+
+
+def dssm_sparse_linear_fwd(cols, vals, lod, W, bias, relu=False, status=None, out=None):
+    """rec_dssm_sparse_linear_fwd: Y [rows, n] = act(bias + sum_j vals[j] W[cols[j], :]); W [in_dim, n] (row stride allowed)."""
+    R, nnz = _dssm_csr(cols, vals, lod, "dssm_sparse_linear_fwd")
+    ldw = _chk_mat(W, "W")
+    T, N = W.shape
+    _chk(bias, torch.float32, "bias")
+    if bias.numel() != N:
+        raise RecError("dssm_sparse_linear_fwd: bias must have n = %d elements" % N)
+    if out is None:
+        out = torch.empty(R, N, dtype=torch.float32, device=W.device)
+    ldy = _chk_mat(out, "out")
+    if tuple(out.shape) != (R, N):
+        raise RecError("dssm_sparse_linear_fwd: out has shape %s, expected %s" % (tuple(out.shape), (R, N)))
+    check(lib().rec_dssm_sparse_linear_fwd(R, nnz, T, N, int(bool(relu)), _p(cols), _p(vals), _p(lod), _p(W), ldw, _p(bias), _p(out),
+                                           ldy, _p(status), _stream()), "rec_dssm_sparse_linear_fwd")
+    return out
+
+
+def dssm_sparse_linear_bwd(vals, row_of, groups, dY, dW):
+    """rec_dssm_sparse_linear_bwd: dW [in_dim, n] (every row written) from the entries grouped by column — groups: the
+    IdGroups of ids_group(cols, in_dim, None, ...) — vals [nnz], row_of [nnz] int32 and dY [rows, n]."""
+    _chk(vals, torch.float32, "vals")
+    _chk(row_of, torch.int32, "row_of")
+    nnz = vals.numel()
+    if groups.n != nnz or row_of.numel() < nnz:
+        raise RecError("dssm_sparse_linear_bwd: groups and row_of must cover the nnz = %d entries" % nnz)
+    lddy, lddw = _chk_mat(dY, "dY"), _chk_mat(dW, "dW")
+    R, N = dY.shape
+    T = dW.shape[0]
+    if dW.shape[1] != N:
+        raise RecError("dssm_sparse_linear_bwd: dW must be [in_dim, %d]" % N)
+    U = min(nnz, T)                                            # the kernel reads at most that many groups, whatever n_uniq says
+    for t, dt, need, name in ((groups.sorted_pos, torch.int32, nnz, "sorted_pos"), (groups.uniq_rows, torch.int64, U, "uniq_rows"),
+                              (groups.seg_offset, torch.int32, U + 1, "seg_offset"), (groups.n_uniq, torch.int32, 1, "n_uniq")):
+        _chk(t, dt, name)
+        if t is None or t.numel() < need:
+            raise RecError("dssm_sparse_linear_bwd: groups.%s must hold at least %d entries" % (name, need))
+    check(lib().rec_dssm_sparse_linear_bwd(R, nnz, T, N, _p(vals), _p(row_of), _p(groups.sorted_pos), _p(groups.uniq_rows),
+                                           _p(groups.seg_offset), _p(groups.n_uniq), _p(dY), lddy, _p(dW), lddw, _stream()),
+          "rec_dssm_sparse_linear_bwd")
+    return dW
+
+
+def dssm_head_step(q, d, slice_end, relu_mask=False, out=None):
+    """rec_dssm_head_step: q [B, n], d [(1 + neg) B, n] field-major -> dict(cos [B, 1 + neg], hit_prob [B], loss_terms [B],
+    loss [1], dq [B, n], dd [(1 + neg) B, n]).  out: such a dict from an earlier call of the same shapes, reused."""
+    ldq, ldd = _chk_mat(q, "q"), _chk_mat(d, "d")
+    B, N = q.shape
+    if d.shape[1] != N or (d.shape[0] % B if B else d.shape[0]):
+        raise RecError("dssm_head_step: d must be [(1 + neg) * %d, %d], got %s" % (B, N, tuple(d.shape)))
+    docs = d.shape[0] // B if B else 1
+    if docs < 1:
+        raise RecError("dssm_head_step: d holds no positive rows")
+    if out is None:
+        f32 = dict(dtype=torch.float32, device=q.device)
+        out = dict(cos=torch.empty(B, docs, **f32), hit_prob=torch.empty(B, **f32), loss_terms=torch.empty(B, **f32),
+                   loss=torch.zeros(1, **f32), dq=torch.empty(B, N, **f32), dd=torch.empty(docs * B, N, **f32))
+    for key, shape in (("cos", (B, docs)), ("hit_prob", (B,)), ("loss_terms", (B,)), ("loss", (1,))):
+        _chk(out[key], torch.float32, key, shape)
+    lddq, lddd = _chk_mat(out["dq"], "dq"), _chk_mat(out["dd"], "dd")
+    if tuple(out["dq"].shape) != (B, N) or tuple(out["dd"].shape) != (docs * B, N):
+        raise RecError("dssm_head_step: dq / dd must have the shapes of q / d")
+    check(lib().rec_dssm_head_step(B, docs - 1, N, int(slice_end), int(bool(relu_mask)), _p(q), ldq, _p(d), ldd, _p(out["cos"]),
+                                   _p(out["hit_prob"]), _p(out["loss_terms"]), _p(out["loss"]), _p(out["dq"]), lddq,
+                                   _p(out["dd"]), lddd, _stream()), "rec_dssm_head_step")
+    return out
+
+
+def dssm_cos(q, d, out=None):
+    """rec_dssm_cos: Paddle's cosine_similarity of q [B, n] against d [B, n] -> [B]."""
+    ldq, ldd = _chk_mat(q, "q"), _chk_mat(d, "d")
+    B, N = q.shape
+    if tuple(d.shape) != (B, N):
+        raise RecError("dssm_cos: q and d must have one shape")
+    if out is None:
+        out = torch.empty(B, dtype=torch.float32, device=q.device)
+    _chk(out, torch.float32, "out", (B,))
+    check(lib().rec_dssm_cos(B, N, _p(q), ldq, _p(d), ldd, _p(out), _stream()), "rec_dssm_cos")
+    return out

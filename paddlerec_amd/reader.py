@@ -1235,3 +1235,75 @@ class NcfReader:
         for b in range(len(self)):
             sl = slice(b * self.batch_size, (b + 1) * self.batch_size)
             yield self.users[sl].view(-1, 1), self.items[sl].view(-1, 1), self.labels[sl].view(-1, 1)
+
+
+def dssm_parse(file_list, fields=None):
+    """dssm/bq_reader_train.py:26-48 (fields=None: every field of a line) and bq_reader_infer.py (fields=2): a line is
+    tab-separated fields, a field a comma-separated float vector -> one list of float32 arrays per line, in file order."""
+    out = []
+    for path in file_list:
+        with open(path, "r") as rf:
+            for line in rf:
+                features = line.rstrip("\n").split("\t")
+                out.append([np.array([float(x) for x in f.split(",")]).astype("float32")
+                            for f in (features if fields is None else features[:fields])])
+    return out
+
+
+def dssm_csr(rows):
+    """Dense float32 vectors -> CSR (cols int64, vals float32, lod int64 [len(rows) + 1], row_of int32): exact zeros are
+    dropped, nothing else is, and a value other than 1.0 is kept."""
+    nz = [np.flatnonzero(r) for r in rows]
+    lod = np.zeros(len(rows) + 1, dtype=np.int64)
+    np.cumsum([len(c) for c in nz], out=lod[1:])
+    cols = np.concatenate(nz).astype(np.int64) if nz else np.zeros(0, np.int64)
+    vals = np.concatenate([r[c] for r, c in zip(rows, nz)]).astype(np.float32) if nz else np.zeros(0, np.float32)
+    row_of = np.repeat(np.arange(len(rows), dtype=np.int32), np.diff(lod))
+    return cols, vals, lod, row_of
+
+
+def dssm_group(cols, width):
+    """The entries of a CSR input grouped by column, on the host, as rec_ids_group(cols, num_rows=width) writes them on the
+    device: sorted_pos int32 [nnz] (entry indices, stably sorted by column), uniq_rows int64 [nnz] (the first U: the distinct
+    columns, ascending), seg_offset int32 [nnz + 1] (sorted_pos[seg_offset[u] : seg_offset[u + 1]] belong to uniq_rows[u]),
+    n_uniq int32 [4] = {U, entries kept, 0, 0}.  A column outside [0, width) is dropped.  A batch that carries these spares
+    its train step the device sort."""
+    cols = np.asarray(cols, np.int64)
+    n = len(cols)
+    keep = np.flatnonzero((cols >= 0) & (cols < width))
+    order = keep[np.argsort(cols[keep], kind="stable")]
+    uniq, counts = np.unique(cols[keep], return_counts=True)
+    sorted_pos, uniq_rows, seg_offset = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int64), np.zeros(n + 1, np.int32)
+    sorted_pos[:len(order)], uniq_rows[:len(uniq)] = order, uniq
+    np.cumsum(counts, out=seg_offset[1:len(uniq) + 1])
+    return sorted_pos, uniq_rows, seg_offset, np.asarray([len(uniq), len(keep), 0, 0], np.int32)
+
+
+class DssmReader:
+    """The reference's DataLoader over dssm/bq_reader_train.py (mode "train": every field — query, positive, negatives) or
+    bq_reader_infer.py (mode "infer": the first two): the lines in file order, batch_size at a time, the last batch short.
+    A batch is [query, docs] in CSR — each (cols, vals, lod, row_of) followed by dssm_group's four arrays, on the device, docs
+    holding the batch's positives first and then each negative field's rows — or, with dense=True, the reference's list of
+    [b, trigram_d] float32 tensors."""
+
+    def __init__(self, file_list, batch_size, device="cuda", mode="train", dense=False):
+        self.batch_size, self.device, self.dense = int(batch_size), device, dense
+        self.lines = dssm_parse(file_list, None if mode == "train" else 2)
+        if len({len(l) for l in self.lines}) > 1 or (self.lines and len(self.lines[0]) < 2):
+            raise ValueError("dssm: every line needs the same number of fields, at least a query and a positive document")
+
+    def __len__(self):
+        return -(-len(self.lines) // self.batch_size)
+
+    def __iter__(self):
+        for b in range(len(self)):
+            lines = self.lines[b * self.batch_size:(b + 1) * self.batch_size]
+            fields = [[l[f] for l in lines] for f in range(len(lines[0]))]
+            if self.dense:
+                yield [torch.from_numpy(np.stack(f)).to(self.device) for f in fields]
+            else:
+                out = []
+                for rows in (fields[0], [r for f in fields[1:] for r in f]):
+                    csr = dssm_csr(rows)
+                    out.append(tuple(torch.from_numpy(a).to(self.device) for a in csr + dssm_group(csr[0], len(rows[0]))))
+                yield out

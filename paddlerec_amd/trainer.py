@@ -10,7 +10,7 @@ What differs by construction: a batch never becomes 28 per-sample NumPy arrays (
 [B,26] / [B,13] device tensors), `loss.backward(); optimizer.step()` is the explicit `train_step` chain of the
 host mirrors, and the AUC buckets stay on the device (read back only when a log line prints them).
 
-    python -m paddlerec_amd.trainer -m <config.yaml> [--model deepfm|fm|ffm|deepfefm|fat_deepffm|wide_deep|dnn|dcn|dcn_v2|gatenet|flen|autofis|din|dien|dmr|bst|xdeepfm|dlrm|mmoe|ple|esmm|escm2|aitm|mind|word2vec|tisas|ensfm|ncf] [-o runner.epochs=1 ...] [--infer]
+    python -m paddlerec_amd.trainer -m <config.yaml> [--model deepfm|fm|ffm|deepfefm|fat_deepffm|wide_deep|dnn|dcn|dcn_v2|gatenet|flen|autofis|din|dien|dmr|bst|xdeepfm|dlrm|mmoe|ple|esmm|escm2|aitm|mind|word2vec|tisas|ensfm|ncf|dssm] [-o runner.epochs=1 ...] [--infer]
     python -m torch.distributed.run --nproc-per-node G -m paddlerec_amd.trainer -m <config.yaml>     # collective mode
 """
 import argparse
@@ -26,7 +26,7 @@ logger = logging.getLogger("paddlerec_amd.trainer")
 
 MODELS = ("deepfm", "fm", "ffm", "deepfefm", "fat_deepffm", "wide_deep", "dnn", "dcn", "dcn_v2", "gatenet", "flen", "autofis",
           "din", "dien", "dmr", "bst", "xdeepfm", "dlrm", "mmoe", "ple", "esmm", "escm2", "aitm", "mind", "word2vec", "tisas",
-          "ensfm", "ncf")
+          "ensfm", "ncf", "dssm")
 
 
 # ------------------------------------------------------------------------------------ configuration
@@ -129,6 +129,8 @@ def _dygraph_model(name):
         from .ensfm import DygraphModel
     elif name == "ncf":
         from .ncf import DygraphModel
+    elif name == "dssm":
+        from .dssm import DygraphModel
     else:
         raise ValueError("unknown model %r (known: %s)" % (name, ", ".join(MODELS)))
     return DygraphModel()
@@ -194,6 +196,8 @@ def create_data_loader(config, model, device, mode="train", shard=None):
         return loader
     if model == "ncf":
         return lambda: iter(reader.NcfReader(files, bs, device))
+    if model == "dssm":
+        return lambda: iter(reader.DssmReader(files, bs, device, "train" if mode == "train" else "infer"))
     if model == "flen":
         return lambda: iter(reader.AvazuReader(files, bs, device, shard=shard))
     if model == "autofis":
@@ -205,6 +209,8 @@ def create_data_loader(config, model, device, mode="train", shard=None):
 
 
 def _batch_size(batch):
+    if isinstance(batch[0], tuple):                   # dssm: a CSR feed (cols, vals, lod, row_of)
+        return int(batch[0][2].numel()) - 1
     return int(batch[0].shape[0])
 
 
@@ -359,7 +365,7 @@ def _apply_optimizer_config(config, model, dy_model):
         logger.info("bst, kept as the reference writes it: %s; preprocess_cmd=%r postprocess_cmd=%r, Dropout(%.2f) with "
                     "the engine's counter-based masks (seed %d)", QUIRKS, dy_model.preprocess_cmd, dy_model.postprocess_cmd,
                     dy_model.dropout_rate, dy_model.dropout_seed)
-    if model in ("mmoe", "ple", "esmm", "escm2", "aitm", "mind", "word2vec", "tisas", "ensfm", "ncf"):
+    if model in ("mmoe", "ple", "esmm", "escm2", "aitm", "mind", "word2vec", "tisas", "ensfm", "ncf", "dssm"):
         import importlib
         logger.info("%s, kept as the reference writes it: %s", model, importlib.import_module("." + model, __package__).QUIRKS)
         if model == "ple":
