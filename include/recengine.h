@@ -2411,6 +2411,53 @@ int rec_dssm_head_step(int64_t batch, int32_t neg, int32_t n, int64_t slice_end,
                        int64_t ld_dq, float* dd, int64_t ld_dd, void* stream);
 int rec_dssm_cos(int64_t batch, int32_t n, const float* q, int64_t ld_q, const float* d, int64_t ld_d, float* cos, void* stream);
 
+/* ----------------------------------------------------------------------------------------
+ * MatchPyramid (models/match/match-pyramid): the interaction image of two sentences, convolved, rectified and max-pooled
+ * (csrc/match_pyramid_ops.hip).  float32; no float atomics; every sum has a fixed order and nothing depends on the order in
+ * which blocks run, so a rerun is bit-identical.  Arguments are checked on the host before any launch (REC_EINVAL, the entry
+ * and the argument named in rec_last_error()); batch == 0 returns REC_OK without a launch after those checks.
+ *
+ * shape: a HOST array of REC_MPYR_SHAPE_LEN int32 = {left_len Ll, right_len Lr, emb_dim E, channels K, filter_h, filter_w,
+ *   pool_h, pool_w, stride_h, stride_w, relu (0: no activation)}; the table has `vocab` rows of row stride ld_table;
+ *   padding_idx -1: none.
+ *   cross[i, j] = <table[left[i]], table[right[j]]>; a padding id, and an id outside [0, vocab), is a zero row (the latter
+ *   sets REC_FLAG_INDEX_OOB in *status, which may be NULL, and reads nothing).  The convolution is stride 1, padding "SAME": k - 1
+ *   zeros per axis, floor((k - 1) / 2) of them in front; conv_w is [K, 1, filter_h, filter_w], conv_b [K].  The pool is VALID:
+ *   PH = (Ll - pool_h) / stride_h + 1, PW likewise; rows and columns beyond the last window are never computed.
+ *   Limits (the LDS staging): Ll <= REC_MPYR_MAX_LEFT, Lr <= REC_MPYR_MAX_RIGHT, E <= REC_MPYR_MAX_EMB, filter_h * filter_w *
+ *   roundup(K, 8) <= REC_MPYR_MAX_WEIGHTS, K * PH * PW <= REC_MPYR_MAX_POOLED, and the band one row of pool windows reads,
+ *   (pool_h + filter_h - 1) * (Lr + filter_w - 1) floats, <= REC_MPYR_MAX_BAND; filter and pool no larger than the image.
+ * rec_mpyr_fwd: left int64 [batch, Ll], right int64 [batch, Lr] -> pooled [batch, K * PH * PW] (ld_pooled) in NCHW order
+ *   (k * PH * PW + ph * PW + pw) and argmax int32 of the same shape (ld_argmax): the cell i * Lr + j that won its window, the
+ *   first in row-major order among equals.  One block per (sample, row of pool windows).
+ * rec_mpyr_bwd: d_pooled (ld_dpooled) and the forward's argmax and inputs -> dL [batch * Ll, E] (ld_dl) and dR [batch * Lr, E]
+ *   (ld_dr), every row written, the rows of padding and out-of-range ids exactly 0; d_conv_w [K * filter_h * filter_w] and
+ *   d_conv_b [K].  A window whose winner's pre-activation is <= 0 under relu passes nothing; a cell that won several windows
+ *   of a channel receives all of them, summed first in ascending window order (at the first of them).  The image is recomputed, not stored.  Two named intermediates: gated [batch, K * PH * PW] (the
+ *   gradient that passes each window) and partials [batch * PH, K * filter_h * filter_w + K] (every block's share of d_conv_w |
+ *   d_conv_b, folded in a fixed order: 16 interleaved ascending sums, then a tree).  d_cross is formed in gather form: a cell sums the windows whose winner's tap
+ *   footprint reaches it in ascending (ph, pw, k).
+ *   batch == 0 launches nothing and leaves every output, d_conv_w and d_conv_b included, untouched.
+ * rec_mpyr_hinge: loss [1] = mean_{r < pairs} max(0, 1 - pred[r] + pred[pairs + r]) (dygraph_model.py:55-69 with pairs = 64);
+ *   d_pred [batch]: -1 / pairs and +1 / pairs for the two rows of an open pair (0 <= the hinge's argument: the gradient flows at
+ *   exactly 0), 0 for a closed one and for rows at or beyond 2 * pairs.  One block, fixed-order fold.  2 * pairs <= batch.
+ * ---------------------------------------------------------------------------------------- */
+#define REC_MPYR_MAX_LEFT 32
+#define REC_MPYR_MAX_RIGHT 1024
+#define REC_MPYR_MAX_EMB 128
+#define REC_MPYR_MAX_WEIGHTS 1024
+#define REC_MPYR_MAX_POOLED 1024
+#define REC_MPYR_MAX_BAND 7168
+#define REC_MPYR_SHAPE_LEN 11
+int rec_mpyr_fwd(int64_t batch, const int32_t* shape, int64_t vocab, int64_t ld_table, int64_t padding_idx, const int64_t* left,
+                 const int64_t* right, const float* table, const float* conv_w, const float* conv_b, float* pooled,
+                 int64_t ld_pooled, int32_t* argmax, int64_t ld_argmax, int32_t* status, void* stream);
+int rec_mpyr_bwd(int64_t batch, const int32_t* shape, int64_t vocab, int64_t ld_table, int64_t padding_idx, const int64_t* left,
+                 const int64_t* right, const float* table, const float* conv_w, const float* conv_b, const float* d_pooled,
+                 int64_t ld_dpooled, const int32_t* argmax, int64_t ld_argmax, float* gated, float* partials, float* dL,
+                 int64_t ld_dl, float* dR, int64_t ld_dr, float* d_conv_w, float* d_conv_b, void* stream);
+int rec_mpyr_hinge(int64_t batch, int64_t pairs, const float* pred, float* loss, float* d_pred, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4443,3 +4443,112 @@ def dssm_cos(q, d, out=None):
     _chk(out, torch.float32, "out", (B,))
     check(lib().rec_dssm_cos(B, N, _p(q), ldq, _p(d), ldd, _p(out), _stream()), "rec_dssm_cos")
     return out
+
+
+# ------------------------------------------------------------------ MatchPyramid (models/match/match-pyramid, csrc/match_pyramid_ops.hip)
+MPYR_MAX_LEFT, MPYR_MAX_RIGHT, MPYR_MAX_EMB = _lib.REC_MPYR_MAX_LEFT, _lib.REC_MPYR_MAX_RIGHT, _lib.REC_MPYR_MAX_EMB
+MPYR_MAX_WEIGHTS, MPYR_MAX_POOLED, MPYR_MAX_BAND = _lib.REC_MPYR_MAX_WEIGHTS, _lib.REC_MPYR_MAX_POOLED, _lib.REC_MPYR_MAX_BAND
+
+MpyrShape = collections.namedtuple("MpyrShape", "left_len right_len emb_dim channels filter_h filter_w pool_h pool_w stride_h "
+                                                "stride_w relu")
+
+
+def mpyr_pooled_shape(shape):
+    """(PH, PW) of the VALID pool of an MpyrShape."""
+    return (shape.left_len - shape.pool_h) // shape.stride_h + 1, (shape.right_len - shape.pool_w) // shape.stride_w + 1
+
+
+def mpyr_shape_error(shape):
+    """None, or why the kernels' LDS staging refuses this MpyrShape (the REC_MPYR_* limits of include/recengine.h)."""
+    s = shape
+    if min(s[:10]) < 1:
+        return "every size must be positive"
+    if s.filter_h > s.left_len or s.filter_w > s.right_len or s.pool_h > s.left_len or s.pool_w > s.right_len:
+        return "filter and pool must fit the [%d, %d] image" % (s.left_len, s.right_len)
+    PH, PW = mpyr_pooled_shape(s)
+    for value, limit, name in ((s.left_len, MPYR_MAX_LEFT, "sentence_left_size"), (s.right_len, MPYR_MAX_RIGHT, "sentence_right_size"),
+                               (s.emb_dim, MPYR_MAX_EMB, "emb_size"),
+                               (s.filter_h * s.filter_w * ((s.channels + 7) // 8 * 8), MPYR_MAX_WEIGHTS, "filter area * kernel_num"),
+                               (s.channels * PH * PW, MPYR_MAX_POOLED, "kernel_num * PH * PW"),
+                               ((s.pool_h + s.filter_h - 1) * (s.right_len + s.filter_w - 1), MPYR_MAX_BAND,
+                                "(pool_h + filter_h - 1) * (sentence_right_size + filter_w - 1)")):
+        if value > limit:
+            return "%s = %d above the kernels' %d" % (name, value, limit)
+    return None
+
+
+def _mpyr_args(shape, left, right, table, conv_w, conv_b, what):
+    _chk(left, torch.int64, "left")
+    _chk(right, torch.int64, "right")
+    _chk(conv_w, torch.float32, "conv_w")
+    _chk(conv_b, torch.float32, "conv_b")
+    E, ldt = _chk_table(table, "table")
+    B = left.shape[0]
+    if tuple(left.shape) != (B, shape.left_len) or tuple(right.shape) != (B, shape.right_len) or E != shape.emb_dim:
+        raise RecError("%s: left / right / table must be [B, %d] / [B, %d] / [V, %d]" % (what, shape.left_len, shape.right_len,
+                                                                                         shape.emb_dim))
+    if conv_w.numel() != shape.channels * shape.filter_h * shape.filter_w or conv_b.numel() != shape.channels:
+        raise RecError("%s: conv_w / conv_b must hold K * kh * kw / K values" % what)
+    return B, ldt, (C.c_int32 * _lib.REC_MPYR_SHAPE_LEN)(*[int(x) for x in shape])
+
+
+def mpyr_fwd(shape, left, right, table, conv_w, conv_b, padding_idx=None, status=None, out=None):
+    """rec_mpyr_fwd: left [B, Ll], right [B, Lr] int64, table [V, E] (row stride allowed) -> (pooled [B, K * PH * PW] float32,
+    argmax int32 of that shape).  out: such a pair (row strides allowed), reused."""
+    B, ldt, arr = _mpyr_args(shape, left, right, table, conv_w, conv_b, "mpyr_fwd")
+    PH, PW = mpyr_pooled_shape(shape)
+    N = shape.channels * max(PH, 0) * max(PW, 0)
+    if out is None:
+        out = (torch.empty(B, N, dtype=torch.float32, device=left.device), torch.empty(B, N, dtype=torch.int32, device=left.device))
+    pooled, argmax = out
+    ldp = _chk_mat(pooled, "pooled")
+    if argmax.dtype != torch.int32 or argmax.dim() != 2 or (argmax.shape[1] > 1 and argmax.stride(1) != 1) \
+            or tuple(pooled.shape) != (B, N) or tuple(argmax.shape) != (B, N):
+        raise RecError("mpyr_fwd: pooled / argmax must be float32 / int32 [%d, %d]" % (B, N))
+    lda = argmax.stride(0) if B > 1 else max(N, 1)
+    check(lib().rec_mpyr_fwd(B, arr, table.shape[0], ldt, -1 if padding_idx is None else int(padding_idx), _p(left), _p(right),
+                             _p(table), _p(conv_w), _p(conv_b), _p(pooled), ldp, _p(argmax), lda, _p(status), _stream()),
+          "rec_mpyr_fwd")
+    return pooled, argmax
+
+
+def mpyr_bwd(shape, left, right, table, conv_w, conv_b, d_pooled, argmax, dL, dR, d_conv_w, d_conv_b, padding_idx=None,
+             scratch=None):
+    """rec_mpyr_bwd -> (dL [B * Ll, E], dR [B * Lr, E], d_conv_w, d_conv_b), all written in place (dL / dR may be row-strided
+    views).  scratch: the dict of the two named intermediates (gated, partials) of an earlier call of this shape, reused."""
+    B, ldt, arr = _mpyr_args(shape, left, right, table, conv_w, conv_b, "mpyr_bwd")
+    PH, PW = mpyr_pooled_shape(shape)
+    N, T = shape.channels * PH * PW, shape.channels * shape.filter_h * shape.filter_w
+    lddp, lddl, lddr = _chk_mat(d_pooled, "d_pooled"), _chk_mat(dL, "dL"), _chk_mat(dR, "dR")
+    _chk(d_conv_w, torch.float32, "d_conv_w")
+    _chk(d_conv_b, torch.float32, "d_conv_b")
+    if tuple(d_pooled.shape) != (B, N) or tuple(argmax.shape) != (B, N) or argmax.dtype != torch.int32:
+        raise RecError("mpyr_bwd: d_pooled / argmax must be float32 / int32 [%d, %d]" % (B, N))
+    if tuple(dL.shape) != (B * shape.left_len, shape.emb_dim) or tuple(dR.shape) != (B * shape.right_len, shape.emb_dim):
+        raise RecError("mpyr_bwd: dL / dR must be [B * Ll, E] / [B * Lr, E]")
+    if d_conv_w.numel() != T or d_conv_b.numel() != shape.channels:
+        raise RecError("mpyr_bwd: d_conv_w / d_conv_b must hold K * kh * kw / K values")
+    lda = argmax.stride(0) if B > 1 else max(N, 1)
+    if scratch is None:
+        scratch = {}
+    if "gated" not in scratch or scratch["gated"].numel() < B * N or scratch["partials"].numel() < B * PH * (T + shape.channels):
+        scratch["gated"] = torch.empty(max(B * N, 1), dtype=torch.float32, device=left.device)
+        scratch["partials"] = torch.empty(max(B * PH * (T + shape.channels), 1), dtype=torch.float32, device=left.device)
+    check(lib().rec_mpyr_bwd(B, arr, table.shape[0], ldt, -1 if padding_idx is None else int(padding_idx), _p(left), _p(right),
+                             _p(table), _p(conv_w), _p(conv_b), _p(d_pooled), lddp, _p(argmax), lda, _p(scratch["gated"]),
+                             _p(scratch["partials"]), _p(dL), lddl, _p(dR), lddr, _p(d_conv_w), _p(d_conv_b), _stream()),
+          "rec_mpyr_bwd")
+    return dL, dR, d_conv_w, d_conv_b
+
+
+def mpyr_hinge(pred, pairs, out=None):
+    """rec_mpyr_hinge: pred [B, 1] or [B] -> (loss [1], d_pred [B]); out: such a pair, reused."""
+    _chk(pred, torch.float32, "pred")
+    B = pred.numel()
+    if out is None:
+        out = (torch.empty(1, dtype=torch.float32, device=pred.device), torch.empty(B, dtype=torch.float32, device=pred.device))
+    loss, d_pred = out
+    _chk(loss, torch.float32, "loss", (1,))
+    _chk(d_pred, torch.float32, "d_pred", (B,))
+    check(lib().rec_mpyr_hinge(B, int(pairs), _p(pred), _p(loss), _p(d_pred), _stream()), "rec_mpyr_hinge")
+    return loss, d_pred

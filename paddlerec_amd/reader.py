@@ -1307,3 +1307,38 @@ class DssmReader:
                     csr = dssm_csr(rows)
                     out.append(tuple(torch.from_numpy(a).to(self.device) for a in csr + dssm_group(csr[0], len(rows[0]))))
                 yield out
+
+
+def letor_parse(file_list):
+    """The parse of match-pyramid/letor_reader.py: a line holds the left and the right sentence, tab-separated, each a
+    comma-separated list of word ids -> (left, right) int64 [lines, Ll] / [lines, Lr], in file order.  Every line must hold the
+    same two lengths (the reference's DataLoader stacks them)."""
+    sentences = ([], [])
+    for path in file_list:
+        with open(path) as f:
+            for line in f:
+                for side, text in zip(sentences, line.rstrip("\n").split("\t")[:2]):
+                    side.append(np.array(text.split(","), dtype=np.int64))
+    if any(len({len(x) for x in side}) > 1 for side in sentences) or len(sentences[0]) != len(sentences[1]):
+        raise ValueError("match-pyramid: every line needs two sentences of the same sentence lengths")
+    if not sentences[0]:
+        return np.zeros((0, 0), np.int64), np.zeros((0, 0), np.int64)
+    return np.stack(sentences[0]), np.stack(sentences[1])
+
+
+class LetorReader:
+    """The reference's DataLoader over match-pyramid/letor_reader.py: the lines in file order, batch_size at a time, the last
+    batch short.  A batch is [sentence_left int64 [b, Ll], sentence_right int64 [b, Lr]] on the device."""
+
+    def __init__(self, file_list, batch_size, device="cuda"):
+        self.batch_size, self.device = int(batch_size), device
+        left, right = letor_parse(file_list)
+        self.left, self.right = torch.from_numpy(left).to(device), torch.from_numpy(right).to(device)
+
+    def __len__(self):
+        return -(-self.left.shape[0] // self.batch_size)
+
+    def __iter__(self):
+        for b in range(len(self)):
+            sl = slice(b * self.batch_size, (b + 1) * self.batch_size)
+            yield [self.left[sl], self.right[sl]]

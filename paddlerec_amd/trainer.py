@@ -10,7 +10,7 @@ What differs by construction: a batch never becomes 28 per-sample NumPy arrays (
 [B,26] / [B,13] device tensors), `loss.backward(); optimizer.step()` is the explicit `train_step` chain of the
 host mirrors, and the AUC buckets stay on the device (read back only when a log line prints them).
 
-    python -m paddlerec_amd.trainer -m <config.yaml> [--model deepfm|fm|ffm|deepfefm|fat_deepffm|wide_deep|dnn|dcn|dcn_v2|gatenet|flen|autofis|din|dien|dmr|bst|xdeepfm|dlrm|mmoe|ple|esmm|escm2|aitm|mind|word2vec|tisas|ensfm|ncf|dssm] [-o runner.epochs=1 ...] [--infer]
+    python -m paddlerec_amd.trainer -m <config.yaml> [--model deepfm|fm|ffm|deepfefm|fat_deepffm|wide_deep|dnn|dcn|dcn_v2|gatenet|flen|autofis|din|dien|dmr|bst|xdeepfm|dlrm|mmoe|ple|esmm|escm2|aitm|mind|word2vec|tisas|ensfm|ncf|match-pyramid|dssm] [-o runner.epochs=1 ...] [--infer]
     python -m torch.distributed.run --nproc-per-node G -m paddlerec_amd.trainer -m <config.yaml>     # collective mode
 """
 import argparse
@@ -26,7 +26,7 @@ logger = logging.getLogger("paddlerec_amd.trainer")
 
 MODELS = ("deepfm", "fm", "ffm", "deepfefm", "fat_deepffm", "wide_deep", "dnn", "dcn", "dcn_v2", "gatenet", "flen", "autofis",
           "din", "dien", "dmr", "bst", "xdeepfm", "dlrm", "mmoe", "ple", "esmm", "escm2", "aitm", "mind", "word2vec", "tisas",
-          "ensfm", "ncf", "dssm")
+          "ensfm", "ncf", "match-pyramid", "dssm")
 
 
 # ------------------------------------------------------------------------------------ configuration
@@ -131,6 +131,8 @@ def _dygraph_model(name):
         from .ncf import DygraphModel
     elif name == "dssm":
         from .dssm import DygraphModel
+    elif name == "match-pyramid":
+        from .match_pyramid import DygraphModel
     else:
         raise ValueError("unknown model %r (known: %s)" % (name, ", ".join(MODELS)))
     return DygraphModel()
@@ -196,6 +198,8 @@ def create_data_loader(config, model, device, mode="train", shard=None):
         return loader
     if model == "ncf":
         return lambda: iter(reader.NcfReader(files, bs, device))
+    if model == "match-pyramid":
+        return lambda: iter(reader.LetorReader(files, bs, device))
     if model == "dssm":
         return lambda: iter(reader.DssmReader(files, bs, device, "train" if mode == "train" else "infer"))
     if model == "flen":
@@ -365,9 +369,10 @@ def _apply_optimizer_config(config, model, dy_model):
         logger.info("bst, kept as the reference writes it: %s; preprocess_cmd=%r postprocess_cmd=%r, Dropout(%.2f) with "
                     "the engine's counter-based masks (seed %d)", QUIRKS, dy_model.preprocess_cmd, dy_model.postprocess_cmd,
                     dy_model.dropout_rate, dy_model.dropout_seed)
-    if model in ("mmoe", "ple", "esmm", "escm2", "aitm", "mind", "word2vec", "tisas", "ensfm", "ncf", "dssm"):
+    if model in ("mmoe", "ple", "esmm", "escm2", "aitm", "mind", "word2vec", "tisas", "ensfm", "ncf", "match-pyramid", "dssm"):
         import importlib
-        logger.info("%s, kept as the reference writes it: %s", model, importlib.import_module("." + model, __package__).QUIRKS)
+        logger.info("%s, kept as the reference writes it: %s", model,
+                    importlib.import_module("." + model.replace("-", "_"), __package__).QUIRKS)
         if model == "ple":
             logger.info("ple level 0 slot map (slot, expert, input): %s; never called: %s", dy_model.slot_map(0), dy_model.unused())
     if model == "dcn_v2":
