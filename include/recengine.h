@@ -1042,6 +1042,11 @@ int rec_dedup_plan(int64_t n, int32_t num_slots, int64_t num_rows, int64_t paddi
  *     (send_counts[d] rows, HOST array of `world` entries), recv by source rank; asynchronous on `stream`.
  *     A sharded step issues it three times: ids to owners, rows back, row-gradients to owners.
  *   rec_allreduce_sum_f32: the flat dense-gradient bucket.
+ *   rec_alltoall_layout: HOST function, the arithmetic rec_alltoall_exchange does before it enters RCCL, for any
+ *     `world` and without a communicator: {send,recv}_bytes[i] = {send,recv}_counts[i] * row_bytes, {send,recv}_displs[i]
+ *     = the bytes of the peers before i, *total_{send,recv} = the sums (all HOST arrays of `world` entries).  A negative
+ *     count, row_bytes <= 0, world < 1 or a null pointer is REC_EINVAL; a product or a running sum that does not fit
+ *     int64 is REC_ESHAPE (rec_alltoall_exchange returns the same).  A refused call writes none of its outputs.
  * ---------------------------------------------------------------------------------------- */
 int rec_comm_unique_id(void* id128);
 int rec_comm_init(const void* id128, int32_t world, int32_t rank, void** comm);
@@ -1054,6 +1059,9 @@ int rec_comm_available(void);
 int rec_alltoall_exchange(void* comm, const void* send, const int64_t* send_counts, void* recv,
                           const int64_t* recv_counts, int32_t row_bytes, void* stream);
 int rec_allreduce_sum_f32(void* comm, float* buf, int64_t n, void* stream);
+int rec_alltoall_layout(int32_t world, const int64_t* send_counts, const int64_t* recv_counts, int32_t row_bytes,
+                        int64_t* send_bytes, int64_t* send_displs, int64_t* recv_bytes, int64_t* recv_displs,
+                        int64_t* total_send, int64_t* total_recv);
 
 /* Row H — feature hash, HOST function: xxh32(str(field_idx)+value) % hash_dim
  * (models/rank/dnn/benchmark_reader.py:52).  `bytes` = the concatenated string. */
@@ -1135,7 +1143,11 @@ int rec_cast_f32_i64(int64_t n, const float* src, int64_t src_stride, int64_t* d
  * rings (ring_bytes each, a power of two; the copy wraps) and pace themselves so that the launch lasts bytes / gbytes_per_s + fixed_us
  * — what an RCCL all-to-all over xGMI is to the rest of the chip: a few resident workgroups moving bytes at the links'
  * rate.  paddlerec_amd/sharded.py issues it where the collectives of a world-1 run sit (REC_EMULATE_LINKS=<G>), so that
- * ONE GPU can show whether the exchange of a G-GPU step fits beside the dW GEMMs. */
+ * ONE GPU can show whether the exchange of a G-GPU step fits beside the dW GEMMs.
+ * The launch holds its workgroups for the modelled duration fixed_us + bytes / (gbytes_per_s * 1e3) microseconds whatever
+ * the copy manages, so a call whose modelled duration exceeds 1 s (rec_stream_spin's limit) is REC_EINVAL, as are a rate
+ * <= 0, fixed_us < 0, blocks outside 1..64, a ring that is no power of two in [64 KB, 2^31] and a src / dst that is null
+ * or not 16-byte aligned — all of it checked on the host before any HIP call. */
 int rec_link_emulate(size_t bytes, float gbytes_per_s, float fixed_us, int32_t blocks, const void* src, void* dst,
                      size_t ring_bytes, void* stream);
 

@@ -123,6 +123,41 @@ extern "C" int rec_comm_size(void* comm, int32_t* world) {
 // 1 when RCCL's entry points resolve in this process (rec_comm_* usable), else 0.  Never fails.
 extern "C" int rec_comm_available(void) { return rccl().ok ? 1 : 0; }
 
+// Host arithmetic of the all-to-all(v): counts in rows of row_bytes bytes -> bytes and running displacements per peer
+// (HOST arrays of `world` entries), and the two totals.  Touches neither RCCL nor HIP, so it can be checked at any world
+// size without a communicator.  Everything is validated BEFORE the first output is written: a refused call leaves the
+// outputs as they were.
+extern "C" int rec_alltoall_layout(int32_t world, const int64_t* send_counts, const int64_t* recv_counts,
+                                   int32_t row_bytes, int64_t* send_bytes, int64_t* send_displs, int64_t* recv_bytes,
+                                   int64_t* recv_displs, int64_t* total_send, int64_t* total_recv) {
+  REC_REQUIRE(world >= 1 && row_bytes > 0, REC_EINVAL, "rec_alltoall_layout: world %d, row_bytes %d: both must be >= 1",
+              (int)world, (int)row_bytes);
+  REC_REQUIRE(send_counts && recv_counts && send_bytes && send_displs && recv_bytes && recv_displs && total_send &&
+                  total_recv, REC_EINVAL, "rec_alltoall_layout: null array");
+  int64_t so = 0, ro = 0;
+  for (int i = 0; i < world; ++i) {
+    REC_REQUIRE(send_counts[i] >= 0 && recv_counts[i] >= 0, REC_EINVAL, "rec_alltoall_layout: negative count at peer %d",
+                i);
+    int64_t sb = 0, rb = 0;
+    REC_REQUIRE(!__builtin_mul_overflow(send_counts[i], (int64_t)row_bytes, &sb) &&
+                    !__builtin_mul_overflow(recv_counts[i], (int64_t)row_bytes, &rb) &&
+                    !__builtin_add_overflow(so, sb, &so) && !__builtin_add_overflow(ro, rb, &ro),
+                REC_ESHAPE, "rec_alltoall_layout: byte count or displacement of peer %d does not fit int64", i);
+  }
+  so = ro = 0;
+  for (int i = 0; i < world; ++i) {
+    send_bytes[i] = send_counts[i] * row_bytes;
+    recv_bytes[i] = recv_counts[i] * row_bytes;
+    send_displs[i] = so;
+    recv_displs[i] = ro;
+    so += send_bytes[i];
+    ro += recv_bytes[i];
+  }
+  *total_send = so;
+  *total_recv = ro;
+  return REC_OK;
+}
+
 // send: rows grouped by destination rank (send_counts[d] rows to rank d, ascending d); recv: rows grouped by source.
 // Counts are HOST arrays of `world` entries, in rows of row_bytes bytes.
 extern "C" int rec_alltoall_exchange(void* comm, const void* send, const int64_t* send_counts, void* recv,
@@ -132,21 +167,18 @@ extern "C" int rec_alltoall_exchange(void* comm, const void* send, const int64_t
   REC_REQUIRE(r.ok, REC_ENCCL, "RCCL is not available in this process");
   int world = 0;
   if (int rc = r.comm_count(comm, &world)) return nccl_fail("ncclCommCount", rc);
-  std::vector<size_t> sc(world), sd(world), rc_(world), rd(world);
-  size_t so = 0, ro = 0;
-  for (int i = 0; i < world; ++i) {
-    REC_REQUIRE(send_counts[i] >= 0 && recv_counts[i] >= 0, REC_EINVAL, "negative count");
-    sc[i] = (size_t)send_counts[i] * row_bytes;
-    rc_[i] = (size_t)recv_counts[i] * row_bytes;
-    sd[i] = so;
-    rd[i] = ro;
-    so += sc[i];
-    ro += rc_[i];
-  }
+  REC_REQUIRE(world >= 1, REC_ENCCL, "ncclCommCount reported %d ranks", world);
+  std::vector<int64_t> lay(4 * (size_t)world);
+  int64_t so = 0, ro = 0;
+  if (int rc = rec_alltoall_layout(world, send_counts, recv_counts, row_bytes, lay.data(), lay.data() + world,
+                                   lay.data() + 2 * world, lay.data() + 3 * world, &so, &ro))
+    return rc;
   REC_REQUIRE((so == 0 || send) && (ro == 0 || recv), REC_EINVAL, "null buffer with a non-zero count");
   if (so == 0 && ro == 0 && world == 1) return REC_OK;
-  if (int rc = r.alltoallv(send, sc.data(), sd.data(), recv, rc_.data(), rd.data(), kNcclInt8, comm,
-                           (hipStream_t)stream))
+  static_assert(sizeof(size_t) == sizeof(int64_t), "RCCL takes size_t counts and displacements");
+  std::vector<size_t> sz(lay.begin(), lay.end());      // non-negative by construction
+  const size_t *sc = sz.data(), *sd = sc + world, *rc_ = sd + world, *rd = rc_ + world;
+  if (int rc = r.alltoallv(send, sc, sd, recv, rc_, rd, kNcclInt8, comm, (hipStream_t)stream))
     return nccl_fail("ncclAllToAllv", rc);
   return REC_OK;
 }
@@ -204,6 +236,11 @@ __global__ __launch_bounds__(256) void link_emulate_kernel(const char* __restric
 extern "C" int rec_link_emulate(size_t bytes, float gbytes_per_s, float fixed_us, int32_t blocks, const void* src,
                                 void* dst, size_t ring_bytes, void* stream) {
   REC_REQUIRE(gbytes_per_s > 0.f && fixed_us >= 0.f && blocks >= 1 && blocks <= 64, REC_EINVAL, "bad arguments");
+  // the launch holds its workgroups for the modelled time whatever else happens: bounded like rec_stream_spin, and
+  // before any HIP call (written so that a NaN is refused as well)
+  const double modelled_us = (double)fixed_us + (double)bytes / ((double)gbytes_per_s * 1e3);
+  REC_REQUIRE(modelled_us <= 1e6, REC_EINVAL, "rec_link_emulate: modelled duration %.0f us exceeds the limit of 1 s",
+              modelled_us);
   REC_REQUIRE(src && dst && ring_bytes >= 65536 && ring_bytes <= (1u << 31) && (ring_bytes & (ring_bytes - 1)) == 0 &&
                   ((uintptr_t)src) % 16 == 0 && ((uintptr_t)dst) % 16 == 0, REC_EINVAL,
               "src / dst: 16-byte aligned rings of a power of two >= 64 KB");

@@ -310,6 +310,10 @@ class Comm:
             h = t.cpu()
             self.dist.all_reduce(h, group=g)
             t.copy_(h)
+        elif not t.is_contiguous():       # torch's NCCL binding refuses a strided tensor ("Tensors must be contiguous")
+            c = t.contiguous()
+            self.dist.all_reduce(c, group=g)
+            t.copy_(c)
         else:
             self.dist.all_reduce(t, group=g)
         return t
