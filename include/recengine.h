@@ -884,6 +884,25 @@ typedef struct {
   int32_t flags;  /* REC_GEMM_ROUTE_* bits */
 } rec_gemm_route;
 int rec_gemm_last_route(rec_gemm_route* out);
+/* Which kernels the calling thread's calls launched, for the entry points that route on the host by row width,
+ * strides, pointer alignment and process environment (host bookkeeping, nothing on the device).  The log is per thread
+ * and OFF by default; while off, a routing decision costs one thread-local flag test and nothing is formatted or stored.
+ *   rec_route_log_begin : clears the calling thread's log and switches it on.
+ *   rec_route_log_end   : switches it off and copies the notes to out, one per launch in call order, each followed by
+ *                         '\n', NUL-terminated.  *needed (may be NULL) receives the bytes that takes.  bytes < *needed is
+ *                         REC_EINVAL: the notes are kept until the next begin, so the call may be repeated with a larger
+ *                         buffer.  Notes past the internal buffer (16 KiB) are never cut silently: REC_ESHAPE.
+ * A note names the kernel template and its arguments:
+ *   rows<VEC,LANES>                  every entry point that dispatches on (emb_dim, row stride): LANES lanes of VEC floats
+ *   adam_rows_narrow<NV,V4,L2>       rec_sparse_adam_rows / _l2, one lane per row: NV float4 groups, float4 row access, decay
+ *   ms_lane<D> | ms_rows<VEC,LANES,NSW,WAVES>           rec_multislot_sumpool_fwd
+ *   ps_narrow<DX> | ps_narrow_whole<row9> | ps_rows<VEC,LANES,statv>   rec_ps_push_rows
+ *   din_fwd:generic | din_fwd:ct:<nopf2|pf2|pf1>:<walk|tickets|split>  rec_din_attention_pool_fwd / _fwd_ws
+ *   din_bwd:generic | din_bwd:ct:<walk|tickets>[:nosplit]              rec_din_attention_pool_bwd / _bwd_ws (nosplit:
+ *                                                                      REC_DIN_TILE_SPLIT=0 holds in this process)
+ * A call refused before it chooses a kernel leaves no note. */
+int rec_route_log_begin(void);
+int rec_route_log_end(char* out, size_t bytes, size_t* needed);
 /* Weight images ahead of time.  Under the bf16 x 3 family every forward / dX call splits op(B) [k, n] into its plane image
  * first (a ~5 us launch per call); the weights of a tower change once per step, so a trainer makes ALL images of the step
  * in one launch right after its optimizer (rec_adam_dense) and passes them as rec_gemm_epilogue_args.b_image.

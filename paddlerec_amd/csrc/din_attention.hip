@@ -1601,6 +1601,7 @@ static int din_fwd_run(const rec_din_desc* d, const int64_t* hist_item, const in
     void (*kern)(DinArgs) = variant == 1   ? din_attention_fwd_ct_kernel<128, 80, 40, false, 2>
                             : variant == 2 ? din_attention_fwd_ct_kernel<128, 80, 40, true, 1>
                                            : din_attention_fwd_ct_kernel<128, 80, 40, true, 2>;
+    const char* variant_name = variant == 1 ? "nopf2" : variant == 2 ? "pf1" : "pf2";
     static bool attr_set[3] = {false, false, false};
     if (!attr_set[variant]) {
       (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kDinCtLdsMax);
@@ -1616,6 +1617,7 @@ static int din_fwd_run(const rec_din_desc* d, const int64_t* hist_item, const in
     static const bool split_env = [] { const char* v = getenv("REC_DIN_TILE_SPLIT"); return !(v && *v == '0'); }();
     if (split_env && need > 0 && workspace && workspace_bytes >= need && tiles <= grid) {
       a.part = (float*)workspace;
+      route_note("din_fwd:ct:%s:split", variant_name);
       hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(kBlock), shmem, (hipStream_t)stream, a);
       GatherJobs riders;
       riders.count = riders.blocks = 0;
@@ -1639,11 +1641,13 @@ static int din_fwd_run(const rec_din_desc* d, const int64_t* hist_item, const in
       REC_REQUIRE(hipMemsetAsync(workspace, 0, sizeof(unsigned int), (hipStream_t)stream) == hipSuccess, REC_EHIP,
                   "hipMemsetAsync failed");
     }
+    route_note("din_fwd:ct:%s:%s", variant_name, a.ticket ? "tickets" : "walk");
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kBlock), shmem, (hipStream_t)stream, a);
     return check_launch("rec_din_attention_pool_fwd");
   }
   int64_t grid = resident_blocks(din_attention_fwd_kernel, kBlock, shmem);
   if (grid > d->batch) grid = d->batch;
+  route_note("din_fwd:generic");
   hipLaunchKernelGGL(din_attention_fwd_kernel, dim3((unsigned)grid), dim3(kBlock), shmem,
                      (hipStream_t)stream, a);
   return check_launch("rec_din_attention_pool_fwd");
@@ -1745,12 +1749,14 @@ static int din_bwd_run(const rec_din_desc* d, const int64_t* hist_item, const in
       REC_REQUIRE(hipMemsetAsync(workspace, 0, sizeof(unsigned int), (hipStream_t)stream) == hipSuccess, REC_EHIP,
                   "hipMemsetAsync failed");
     }
+    route_note("din_bwd:ct:%s%s", g.ticket ? "tickets" : "walk", split_env ? "" : ":nosplit");
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kBlock), Ct::lds_bytes, (hipStream_t)stream, g);
     return check_launch("rec_din_attention_pool_bwd");
   }
   REC_REQUIRE(shmem <= 64 * 1024, REC_ESHAPE, "history too long for the LDS buffers (%zu B)", shmem);
   int64_t grid = resident_blocks(din_attention_bwd_kernel, kBlock, shmem);
   if (grid > d->batch) grid = d->batch;
+  route_note("din_bwd:generic");
   hipLaunchKernelGGL(din_attention_bwd_kernel, dim3((unsigned)grid), dim3(kBlock), shmem,
                      (hipStream_t)stream, g);
   return check_launch("rec_din_attention_pool_bwd");

@@ -7,6 +7,7 @@
 //   rec_xxh32*          <- xxhash.xxh32(str(idx)+feat).intdigest() % hash_dim
 //                          (models/rank/dnn/benchmark_reader.py:52) — XXH32 per its published spec
 #include <stdarg.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <string>
@@ -23,6 +24,37 @@ void set_error(const char* fmt, ...) {
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
+}
+
+// the route log of this thread (rec_common.h: route_note): newline-separated notes, NUL-terminated.  Only the flag lives
+// in every thread's TLS block; the buffer is allocated by the thread's first rec_route_log_begin and freed when it exits.
+constexpr size_t kRouteLogBytes = 16384;
+static thread_local bool t_route_log_on = false;
+static thread_local char* t_route_log = nullptr;
+static thread_local size_t t_route_log_len = 0;
+static thread_local bool t_route_log_cut = false;   // a note did not fit: rec_route_log_end reports it
+struct RouteLogOwner {
+  char* p = nullptr;
+  ~RouteLogOwner() { free(p); }
+};
+static thread_local RouteLogOwner t_route_log_owner;   // touched by rec_route_log_begin only
+
+void route_note(const char* fmt, ...) {
+  if (!t_route_log_on) return;
+  if (t_route_log_cut) return;
+  const size_t room = kRouteLogBytes - t_route_log_len;   // >= 1: the terminator
+  va_list ap;
+  va_start(ap, fmt);
+  const int n = vsnprintf(t_route_log + t_route_log_len, room, fmt, ap);
+  va_end(ap);
+  if (n < 0 || (size_t)n + 2 > room) {                    // note + '\n' + NUL
+    t_route_log[t_route_log_len] = 0;
+    t_route_log_cut = true;
+    return;
+  }
+  t_route_log_len += (size_t)n;
+  t_route_log[t_route_log_len++] = '\n';
+  t_route_log[t_route_log_len] = 0;
 }
 
 constexpr int kLossBlocks = 1024;
@@ -250,6 +282,30 @@ using namespace rec;
 
 extern "C" const char* rec_last_error(void) { return rec::g_err; }
 extern "C" int rec_version(void) { return 100; }
+
+extern "C" int rec_route_log_begin(void) {
+  if (!rec::t_route_log_owner.p) rec::t_route_log_owner.p = (char*)malloc(rec::kRouteLogBytes);
+  REC_REQUIRE(rec::t_route_log_owner.p, REC_EINVAL, "route log: out of memory");
+  rec::t_route_log = rec::t_route_log_owner.p;
+  rec::t_route_log[0] = 0;
+  rec::t_route_log_len = 0;
+  rec::t_route_log_cut = false;
+  rec::t_route_log_on = true;
+  return REC_OK;
+}
+
+extern "C" int rec_route_log_end(char* out, size_t bytes, size_t* needed) {
+  rec::t_route_log_on = false;
+  const size_t len = rec::t_route_log ? rec::t_route_log_len : 0;   // a thread that never began: the empty log
+  if (needed) *needed = len + 1;
+  REC_REQUIRE(!rec::t_route_log_cut, REC_ESHAPE, "route log: more than %zu bytes of notes between begin and end",
+              rec::kRouteLogBytes);
+  REC_REQUIRE(out && bytes > len, REC_EINVAL, "route log: out holds %zu bytes, the notes need %zu",
+              out ? bytes : (size_t)0, len + 1);
+  if (len) memcpy(out, rec::t_route_log, len);
+  out[len] = 0;
+  return REC_OK;
+}
 
 extern "C" int rec_logloss_workspace_bytes(int64_t batch, size_t* bytes) {
   REC_REQUIRE(bytes && batch >= 0, REC_EINVAL, "bad arguments");

@@ -641,6 +641,7 @@ extern "C" int rec_multislot_sumpool_fwd(const rec_multislot_desc* d, const int6
     REC_REQUIRE(grid < (1ll << 31), REC_ESHAPE, "too many tiles");                                       \
     const int vec_out = out_stride % 4 == 0 && ((uintptr_t)out) % 16 == 0 && S % 4 == 0 &&               \
                         (!counts || ((uintptr_t)counts) % 16 == 0);                                      \
+    route_note("ms_lane<%d>", DT_);                                                                      \
     hipLaunchKernelGGL((multislot_sumpool_lane_kernel<DT_, NSW_, W_>), dim3((unsigned)grid),             \
                        dim3(W_ * kWave), shmem, st, d->batch, S, d->row_stride, d->key_mode,             \
                        d->num_rows, d->padding_idx, lod_stride, out_stride, nsg, vec_out, fmod, values,  \
@@ -666,6 +667,7 @@ extern "C" int rec_multislot_sumpool_fwd(const rec_multislot_desc* d, const int6
     REC_REQUIRE(grid < (1ll << 31), REC_ESHAPE, "too many tiles");                                      \
     REC_REQUIRE(shmem <= 160 * 1024, REC_ESHAPE, "LDS tile %zu B too large", shmem);                    \
     auto kern = multislot_sumpool_kernel<V, L, NSW_, W_>;                                               \
+    route_note("ms_rows<%d,%d,%d,%d>", V, L, NSW_, W_);                                                 \
     if (shmem > 64 * 1024)                                                                              \
       (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem); \
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kMsBlock),                                      \

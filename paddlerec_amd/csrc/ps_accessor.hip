@@ -465,8 +465,12 @@ extern "C" int rec_ps_push_rows(int64_t n_max, int32_t num_slots, const rec_ps_l
     int64_t grid = (n_max + kBlock - 1) / kBlock;
     if (grid > (int64_t)kNumCU * 32) grid = (int64_t)kNumCU * 32;   // grid-stride loop in the kernel
 #define REC_PS_NARROW(DX_)                                                                               \
-  hipLaunchKernelGGL((ps_push_rows_narrow_kernel<DX_>), dim3((unsigned)grid), dim3(kBlock), 0, st, *layout, \
-                     num_slots, n_uniq, uniq_rows, seg_offset, sorted_pos, gx, gw, show, click, rec, *accessor, false)
+  do {                                                                                                   \
+    route_note("ps_narrow<%d>", DX_);                                                                    \
+    hipLaunchKernelGGL((ps_push_rows_narrow_kernel<DX_>), dim3((unsigned)grid), dim3(kBlock), 0, st, *layout, \
+                       num_slots, n_uniq, uniq_rows, seg_offset, sorted_pos, gx, gw, show, click, rec, *accessor, \
+                       false);                                                                           \
+  } while (0)
     static const bool whole_env = [] { const char* v = getenv("REC_PS_WHOLE_RECORD"); return !(v && *v == '0'); }();
     const bool whole = whole_env && layout->row_stride == 16 && layout->embed_off == 0 && layout->embedx_off == 1 &&
                        layout->embedx_dim == 8 && layout->stat_off == 9 && ((uintptr_t)rec) % 16 == 0;
@@ -474,10 +478,11 @@ extern "C" int rec_ps_push_rows(int64_t n_max, int32_t num_slots, const rec_ps_l
     const bool row9 = gx.grad == gw.grad && gx.pitch == 9 && gw.pitch == 9 && gx.col == 1 && gw.col == 0 &&
                       gx.gl.div == gw.gl.div && gx.gl.group == gw.gl.group && gx.gl.group_stride == gw.gl.group_stride &&
                       gx.gl.index == gw.gl.index;
-    if (whole)
+    if (whole) {
+      route_note("ps_narrow_whole<%d>", (int)row9);
       hipLaunchKernelGGL((ps_push_rows_narrow_kernel<8, true>), dim3((unsigned)grid), dim3(kBlock), 0, st, *layout,
                          num_slots, n_uniq, uniq_rows, seg_offset, sorted_pos, gx, gw, show, click, rec, *accessor, row9);
-    else if (Dx <= 4) REC_PS_NARROW(4); else if (Dx <= 8) REC_PS_NARROW(8);
+    } else if (Dx <= 4) REC_PS_NARROW(4); else if (Dx <= 8) REC_PS_NARROW(8);
     else if (Dx <= 12) REC_PS_NARROW(12); else REC_PS_NARROW(16);
 #undef REC_PS_NARROW
     return check_launch("rec_ps_push_rows (narrow)");
@@ -489,6 +494,7 @@ extern "C" int rec_ps_push_rows(int64_t n_max, int32_t num_slots, const rec_ps_l
   if (lanes == L_) {                                                                                   \
     const int64_t grid = (n_max * L_ + kBlock - 1) / kBlock;                                           \
     REC_REQUIRE(grid < (1ll << 31), REC_ESHAPE, "too many rows");                                      \
+    route_note("ps_rows<%d,%d,%d>", V, L_, (int)statv);                                                \
     if (statv)                                                                                         \
       hipLaunchKernelGGL((ps_push_rows_kernel<V, L_, true>), dim3((unsigned)grid), dim3(kBlock), 0, st, \
                          *layout, num_slots, n_uniq, uniq_rows, seg_offset, sorted_pos, gx, gw, show,  \

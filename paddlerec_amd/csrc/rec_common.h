@@ -24,6 +24,11 @@ inline int check_launch(const char* what) {
   return REC_OK;
 }
 
+// Per-thread route log (rec_route_log_begin / rec_route_log_end): a host router that picks a kernel from widths,
+// strides, alignment or the environment notes the kernel it launches, template arguments included, one note per
+// launch.  Off by default; while off a note is one thread-local flag test and formats and stores nothing (head_ops.hip).
+void route_note(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
+
 #define REC_REQUIRE(cond, code, ...) \
   do {                               \
     if (!(cond)) {                   \
@@ -149,8 +154,11 @@ template <class F>
 inline int dispatch_row_shape(int D, int stride, F&& f) {
   const bool v4 = (D % 4 == 0) && (stride % 4 == 0);
   const int lanes = pow2_ceil(v4 ? D / 4 : D);
-#define REC_CASE(V, L) \
-  if (lanes == L) return f(std::integral_constant<int, V>{}, std::integral_constant<int, L>{});
+#define REC_CASE(V, L)                                                                \
+  if (lanes == L) {                                                                   \
+    route_note("rows<%d,%d>", V, L);                                                  \
+    return f(std::integral_constant<int, V>{}, std::integral_constant<int, L>{});     \
+  }
   if (v4) {
     REC_CASE(4, 1) REC_CASE(4, 2) REC_CASE(4, 4) REC_CASE(4, 8) REC_CASE(4, 16) REC_CASE(4, 32)
     REC_CASE(4, 64)
@@ -171,6 +179,7 @@ template <class F>
 inline int dispatch_row_shape_wide(int D, int stride, F&& f) {
   const bool v4 = (D % 4 == 0) && (stride % 4 == 0);
   if (v4 && D > 4 * 64 && D <= 4 * 256) {
+    route_note("rows<4,%d>", D <= 4 * 128 ? 128 : 256);
     if (D <= 4 * 128) return f(std::integral_constant<int, 4>{}, std::integral_constant<int, 128>{});
     return f(std::integral_constant<int, 4>{}, std::integral_constant<int, 256>{});
   }

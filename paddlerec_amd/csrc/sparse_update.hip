@@ -1808,9 +1808,12 @@ static int sparse_adam_rows_impl(int64_t n_max, int32_t emb_dim, int32_t row_str
     if (grid > (int64_t)kNumCU * 32) grid = (int64_t)kNumCU * 32;   // grid-stride loop in the kernel
     const int nv = (emb_dim + 3) / 4;
 #define REC_NARROW_L2(NV_, V4_, L2_)                                                                          \
-  hipLaunchKernelGGL((sparse_adam_rows_narrow_kernel<NV_, V4_, L2_>), dim3((unsigned)grid), dim3(kBlock), 0, st, \
-                     emb_dim, row_stride, state_stride, n_uniq, uniq_rows, seg_offset, sorted_pos, grad, gl,      \
-                     grad_scale, P, M, V, lr_t, eps_t, hyper->beta1, hyper->beta2, l2)
+  do {                                                                                                        \
+    route_note("adam_rows_narrow<%d,%d,%d>", NV_, (int)V4_, (int)L2_);                                        \
+    hipLaunchKernelGGL((sparse_adam_rows_narrow_kernel<NV_, V4_, L2_>), dim3((unsigned)grid), dim3(kBlock), 0, st, \
+                       emb_dim, row_stride, state_stride, n_uniq, uniq_rows, seg_offset, sorted_pos, grad, gl,    \
+                       grad_scale, P, M, V, lr_t, eps_t, hyper->beta1, hyper->beta2, l2);                         \
+  } while (0)
 #define REC_NARROW(NV_, V4_)                                         \
   do {                                                               \
     if (l2 != 0.f) REC_NARROW_L2(NV_, V4_, true); else REC_NARROW_L2(NV_, V4_, false); \

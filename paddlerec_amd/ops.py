@@ -5,6 +5,7 @@ librecengine.so.  Tensors must live on a ROCm device — there is deliberately n
 Reference call sites are cited in include/recengine.h next to each entry point.
 """
 import collections
+import contextlib
 import ctypes as C
 import os
 
@@ -3661,6 +3662,22 @@ def gemm_last_route():
     return GemmRouteInfo(_lib.GEMM_ROUTE_FAMILIES[r.family] if r.family >= 0 else None,
                          _lib.GEMM_CFGS[r.cfg] if r.cfg >= 0 else None, r.splits,
                          frozenset(n for n, b in _lib.GEMM_ROUTE_FLAGS.items() if r.flags & b))
+
+
+@contextlib.contextmanager
+def route_log():
+    """Which kernels this thread's calls launch inside the block (rec_route_log_begin / rec_route_log_end): yields a
+    list that holds, once the block is left, one note per launch of a host-routed entry point, in call order
+    ("rows<4,16>", "ms_lane<9>", "din_fwd:ct:nopf2:split", ... — include/recengine.h names them all).  The log is off
+    outside such a block; blocks do not nest."""
+    notes = []
+    check(_lib.lib().rec_route_log_begin(), "rec_route_log_begin")
+    try:
+        yield notes
+    finally:
+        buf, need = C.create_string_buffer(1 << 15), C.c_size_t(0)
+        check(_lib.lib().rec_route_log_end(buf, C.c_size_t(len(buf)), C.byref(need)), "rec_route_log_end")
+        notes.extend(buf.value.decode().splitlines())
 
 
 _relu_bits_cache = {}

@@ -21,7 +21,7 @@ import torch
 from . import _lib, ops
 
 _HOST_ONLY = ("rec_last_error", "rec_gemm_plan_splits", "rec_gemm_last_route", "rec_din_saves_act1", "rec_comm_available",
-              "rec_ids_group_plan")
+              "rec_ids_group_plan", "rec_route_log_begin", "rec_route_log_end")
 
 
 class CallPlan:

@@ -102,6 +102,26 @@ def test_gemm_route_report_without_gpu(engine_lib):
     assert tuple(names) == _lib.GEMM_CFGS
 
 
+def test_route_log_without_gpu(engine_lib):
+    """rec_route_log_begin / rec_route_log_end are host bookkeeping: they answer on a GPU-less host.  An empty log is one
+    NUL byte; a buffer that cannot hold the notes is refused and named; a call refused before it chooses a kernel
+    leaves no note; ops.route_log() yields the notes as a list."""
+    import ctypes as C
+    from paddlerec_amd import ops
+    L = engine_lib
+    buf, need = C.create_string_buffer(b"x" * 8, 8), C.c_size_t(99)
+    assert L.rec_route_log_begin() == 0
+    assert L.rec_sparse_adam_rows(10, 16, 8, 0, None, None, None, None, None, None, None, None, None, None, None,
+                                  None) == -1                                       # row_stride < emb_dim: refused
+    assert L.rec_route_log_end(None, 0, C.byref(need)) == -1 and need.value == 1 and b"route log" in L.rec_last_error()
+    assert L.rec_route_log_end(buf, 0, None) == -1
+    assert L.rec_route_log_end(buf, 1, C.byref(need)) == 0 and buf.raw[:1] == b"\0" and need.value == 1
+    assert L.rec_route_log_end(buf, 8, None) == 0 and buf.value == b""                # end without begin: the last log
+    with ops.route_log() as notes:
+        assert notes == []
+    assert notes == []
+
+
 def test_more_argument_validation_without_gpu(engine_lib):
     """Every entry point rejects null pointers / bad sizes before it touches the device."""
     import ctypes as C

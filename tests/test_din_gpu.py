@@ -1,5 +1,9 @@
 """DIN on the HIP kernels: fused attention-pool and the full DINLayer forward against the golden fixture of
 the reference's unmodified din/net.py and the NumPy oracle (oracle/din_ref.py)."""
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 import torch
@@ -9,6 +13,12 @@ from oracle import din_ref as Dn
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
+HERE = os.path.dirname(os.path.abspath(__file__))
+WORKER = os.path.join(HERE, "_din_route_worker.py")
+# the switches din_fwd_run / din_bwd_run (csrc/din_attention.hip) read ONCE per process: a test that means one of them
+# starts a fresh child (_din_route_worker.py); this process runs the defaults, which the route assertions below pin
+LATCHED = ("REC_DIN_TILE_SPLIT", "REC_DIN_TICKETS", "REC_DIN_FWD_VARIANT", "REC_DIN_FWD_GENERIC", "REC_DIN_BWD_GENERIC")
+FWD_CT_WALK, FWD_CT_SPLIT, FWD_CT_TICKETS = ("din_fwd:ct:nopf2:" + r for r in ("walk", "split", "tickets"))
 
 
 def T(a):
@@ -51,8 +61,10 @@ def test_attention_pool_vs_oracle(engine_lib, B, Tn, Ei, Ec):
     ti = np.repeat(rng.integers(1, ni, B)[:, None], Tn, 1); tc = np.repeat(rng.integers(1, nc, B)[:, None], Tn, 1)
     aw = [rng.uniform(-0.2, 0.2, s).astype(np.float32) for s in ((4 * E, 80), (80, 40), (40, 1))]
     ab = [rng.uniform(-0.1, 0.1, s).astype(np.float32) for s in ((80,), (40,), (1,))]
-    out, attw, status = ops.din_attention_pool(T(hi), T(hc), T(ti), T(tc), T(mask), *[T(t) for t in tabs],
-                                               [T(w) for w in aw], [T(b) for b in ab])
+    with ops.route_log() as route:
+        out, attw, status = ops.din_attention_pool(T(hi), T(hc), T(ti), T(tc), T(mask), *[T(t) for t in tabs],
+                                                   [T(w) for w in aw], [T(b) for b in ab])
+    assert route == [FWD_CT_WALK if E == 128 else "din_fwd:generic"]        # no workspace: never split, never tickets
     assert int(status.item()) == 0
     h = np.concatenate([tabs[0][hi], tabs[1][hc]], 2)
     q = np.concatenate([tabs[2][ti], tabs[3][tc]], 2)
@@ -179,10 +191,13 @@ def test_attention_pool_bwd_vs_oracle(engine_lib, B, Tn, Ei, Ec, use_saved):
     dout = rng.standard_normal((B, E)).astype(np.float32)
     taw, tab, tt = [T(w) for w in aw], [T(b) for b in ab], [T(t) for t in tabs]
     saved = {} if use_saved else None
-    out, attw, _ = ops.din_attention_pool(T(hi), T(hc), T(tis), T(tcs), T(mask), *tt, taw, tab, saved=saved)
-    if use_saved:
-        assert (saved["act1"] is not None) == (E == 128)
-    dh, dq = ops.din_attention_pool_bwd(T(hi), T(hc), T(tis), T(tcs), *tt, taw, tab, attw, T(dout), saved=saved)
+    with ops.route_log() as route:
+        out, attw, _ = ops.din_attention_pool(T(hi), T(hc), T(tis), T(tcs), T(mask), *tt, taw, tab, saved=saved)
+        if use_saved:
+            assert (saved["act1"] is not None) == (E == 128)
+        dh, dq = ops.din_attention_pool_bwd(T(hi), T(hc), T(tis), T(tcs), *tt, taw, tab, attw, T(dout), saved=saved)
+    assert route == [FWD_CT_WALK if E == 128 else "din_fwd:generic",
+                     "din_bwd:ct:walk" if E == 128 and use_saved else "din_bwd:generic"]
     h = np.concatenate([tabs[0][hi], tabs[1][hc]], 2)
     q = np.concatenate([tabs[2][tis], tabs[3][tcs]], 2)
     ref = Dn.attention_pool_backward(h.astype(np.float64), q.astype(np.float64), mask.astype(np.float64),
@@ -394,14 +409,143 @@ def test_sparse_sgd_small_equals_group_then_rows(engine_lib, n, D, N, hot):
         assert_close_floor(N_(Pc), want2, want2_32)
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("B,T", [(32, 152), (3, 100), (7, 33), (40, 64)])
-def test_tile_split_forward_and_backward_equal_the_per_sample_walk(engine_lib, monkeypatch, B, T):
-    """Few samples (din/config.yaml batch size 32: fewer than the chip has block slots): the forward runs one block per
-    32-position history tile and a combine launch rescales the per-tile softmax pieces (rec_din_attention_pool_fwd_ws),
-    the backward deals (sample, tile) pairs to the blocks.  Against the same kernels walking a sample's tiles in one
-    block (REC_DIN_TILE_SPLIT=0): pooled output, attention weights and both gradients at fp32 rounding."""
-    from paddlerec_amd import ops
+# ------------------------------------------------------------------------------------------------ routes of the pair
+# din_fwd_run / din_bwd_run choose among: the runtime-shaped kernels (generic); the compile-time-shaped pair (ct) walking
+# a sample's tiles in one block, drawing samples from a ticket word, or (forward) one block per tile + a combine launch.
+# The route log (ops.route_log) says which one ran; every case below asserts it next to the float64 oracle.
+def _check_vs_oracle(p, r, what, fwd=True, bwd=True):
+    """The results of _din_route_worker.run against oracle/din_ref.py, at the bars of test_attention_pool_vs_oracle and
+    test_attention_pool_bwd_vs_oracle."""
+    tabs, mask = [p["tab%d" % k] for k in range(4)], p["mask"]
+    aw, ab = [p["aw%d" % k] for k in range(3)], [p["ab%d" % k] for k in range(3)]
+    h = np.concatenate([tabs[0][p["hi"]], tabs[1][p["hc"]]], 2)
+    q = np.concatenate([tabs[2][p["tis"]], tabs[3][p["tcs"]]], 2)
+    assert int(r["status"].reshape(-1)[0]) == 0, what
+    if fwd:
+        want, wts = Dn.attention_pool(h, q, mask.astype(np.float32), aw, ab, return_weights=True)
+        np.testing.assert_allclose(r["out"], want, rtol=1e-5, atol=2e-6, err_msg=what)
+        assert_close_scaled(r["attw"], wts, 1e-5, err_msg=what)
+        assert np.all(r["attw"][mask != 0] == 0.0), what
+        np.testing.assert_allclose(r["attw"].sum(1), 1.0, rtol=1e-5, err_msg=what)
+    if bwd:
+        f64 = lambda xs: [x.astype(np.float64) for x in xs]
+        ref = Dn.attention_pool_backward(h.astype(np.float64), q.astype(np.float64), mask.astype(np.float64), f64(aw),
+                                         f64(ab), p["dout"].astype(np.float64))
+        ref32 = Dn.attention_pool_backward(h, q, mask.astype(np.float32), aw, ab, p["dout"])
+        scale = max(np.abs(ref["dh"]).max(), np.abs(ref["dq"]).max())
+        assert_close_floor(r["dh"], ref["dh"], ref32["dh"], err_msg=what + ": dh", scale=scale)
+        assert_close_floor(r["dq"], ref["dq"], ref32["dq"], err_msg=what + ": dq", scale=scale)
+        assert np.all(r["dh"][mask != 0] == 0.0) and np.all(r["dq"][mask != 0] == 0.0), what
+
+
+@pytest.mark.parametrize("name,Ei,Ec,mode,fwd_route,bwd_route", [
+    ("generic", 8, 8, (0, 0, 0), "din_fwd:generic", "din_bwd:generic"),
+    ("generic_ws_saved", 8, 8, (1, 1, 1), "din_fwd:generic", "din_bwd:generic"),    # saves nothing: the backward recomputes
+    ("ct_walk", 64, 64, (0, 1, 0), FWD_CT_WALK, "din_bwd:ct:walk"),
+    ("ct_split", 64, 64, (1, 1, 1), FWD_CT_SPLIT, "din_bwd:ct:walk"),
+    ("ct_fwd_generic_bwd", 64, 64, (0, 0, 0), FWD_CT_WALK, "din_bwd:generic"),       # nothing saved: use_saved=False
+])
+def test_attention_routes_smallest_cases(engine_lib, name, Ei, Ec, mode, fwd_route, bwd_route):
+    """B 2, T 33 (two tiles, the second holding one position), hidden 80-40: the smallest shape on each route of the pair
+    that the default environment can take below the ticket threshold."""
+    import _din_route_worker as W
+    p = W.problem(2, 33, Ei, Ec, seed=233 + Ei)
+    r = W.run(p, *mode)
+    assert r["fwd_route"].tolist() == [fwd_route] and r["bwd_route"].tolist() == [bwd_route]
+    _check_vs_oracle(p, r, name)
+
+
+_TICKET_CASES = {}
+
+
+def _ticket_case(which):
+    """The first of the suite's ticket shape (tests/workspace_cases.py: forward B 2049, backward B 1100, T 33, E 128,
+    80-40) and its 2x and 4x batch whose route log names `tickets` on this chip -> (problem, results); the ticket word
+    needs more samples than the chip has resident blocks, which is the occupancy query's answer."""
+    if which not in _TICKET_CASES:
+        import _din_route_worker as W
+        B0 = dict(fwd=2049, bwd=1100)[which]
+        seen = []
+        for B in (B0, 2 * B0, 4 * B0):
+            p = W.problem(B, 33, 64, 64, seed=B * 33)
+            r = W.run(p, which == "fwd", True, which == "bwd")
+            seen.append((B, r[which + "_route"].tolist()))
+            if "tickets" in seen[-1][1][0]:
+                _TICKET_CASES[which] = (p, r)
+                break
+        else:
+            pytest.fail("no %s shape took the ticket route: %r" % (which, seen))
+    return _TICKET_CASES[which]
+
+
+def test_attention_fwd_ticket_route_vs_oracle(engine_lib):
+    p, r = _ticket_case("fwd")
+    assert r["fwd_route"].tolist() == [FWD_CT_TICKETS]
+    _check_vs_oracle(p, r, "fwd tickets B %d" % p["hi"].shape[0], bwd=False)
+
+
+def test_attention_bwd_ticket_route_vs_oracle(engine_lib):
+    p, r = _ticket_case("bwd")
+    assert r["fwd_route"].tolist() == [FWD_CT_WALK] and r["bwd_route"].tolist() == ["din_bwd:ct:tickets"]
+    assert int(r["saved_act1"]) == 1
+    _check_vs_oracle(p, r, "bwd tickets B %d" % p["hi"].shape[0], fwd=False)
+
+
+def _child(tmp_path, switches, problems):
+    """One fresh process with `switches` in its environment (and no other latched switch) runs `problems`
+    {name: (arrays, (fwd_ws, use_saved, bwd_ws))} -> {name: results}."""
+    import _din_route_worker as W
+    src, dst = str(tmp_path / "in.npz"), str(tmp_path / "out.npz")
+    arrays = {}
+    for name, (p, mode) in problems.items():
+        assert "__" not in name
+        arrays.update({name + "__" + k: np.asarray(p[k]) for k in W.ARRAYS})
+        arrays[name + "__mode"] = np.array(mode, np.int64)
+    np.savez(src, **arrays)
+    env = {k: v for k, v in os.environ.items() if k not in LATCHED}
+    env.update(switches)
+    r = subprocess.run([sys.executable, WORKER, src, dst], env=env, capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, "%r: %s" % (switches, r.stderr[-2000:])
+    got = np.load(dst)
+    return {name: {k[len(name) + 2:]: got[k] for k in got.files if k.startswith(name + "__")} for name in problems}
+
+
+@pytest.mark.parametrize("switches,fwd,bwd", [
+    (dict(REC_DIN_FWD_VARIANT="pf2"), "din_fwd:ct:pf2:%s", "din_bwd:ct:walk"),
+    (dict(REC_DIN_FWD_VARIANT="pf1"), "din_fwd:ct:pf1:%s", "din_bwd:ct:walk"),
+    (dict(REC_DIN_FWD_GENERIC="1"), "din_fwd:generic", "din_bwd:generic"),       # nothing saved for the backward either
+    (dict(REC_DIN_BWD_GENERIC="1"), "din_fwd:ct:nopf2:%s", "din_bwd:generic"),
+], ids=lambda s: "-".join("%s=%s" % kv for kv in s.items()) if isinstance(s, dict) else None)
+def test_attention_under_latched_switches(engine_lib, tmp_path, switches, fwd, bwd):
+    """E 128 / 80-40 at B 7, T 33 with and without a workspace, and the forward at the ticket shape, in a process that
+    has the switch set from its start: the log names the intended kernels and they match the oracle."""
+    import _din_route_worker as W
+    small = W.problem(7, 33, 64, 64, seed=733)
+    tp, _ = _ticket_case("fwd")
+    got = _child(tmp_path, switches, dict(split=(small, (1, 1, 1)), walk=(small, (0, 1, 0)), tickets=(tp, (1, 0, 0))))
+    for name, p in (("split", small), ("walk", small), ("tickets", tp)):
+        r = got[name]
+        assert r["fwd_route"].tolist() == [fwd % name if "%s" in fwd else fwd], (name, r["fwd_route"])
+        if name != "tickets":
+            assert r["bwd_route"].tolist() == [bwd], (name, r["bwd_route"])
+        _check_vs_oracle(p, r, "%r %s" % (switches, name), bwd=name != "tickets")
+
+
+def test_attention_with_tickets_switched_off(engine_lib, tmp_path):
+    """REC_DIN_TICKETS=0 at the shapes that take the ticket route by default: each block walks its fixed share."""
+    pf, _ = _ticket_case("fwd")
+    pb, _ = _ticket_case("bwd")
+    got = _child(tmp_path, dict(REC_DIN_TICKETS="0"), dict(fwd=(pf, (1, 0, 0)), bwd=(pb, (0, 1, 1))))
+    assert got["fwd"]["fwd_route"].tolist() == [FWD_CT_WALK]
+    assert got["bwd"]["bwd_route"].tolist() == ["din_bwd:ct:walk"]
+    _check_vs_oracle(pf, got["fwd"], "REC_DIN_TICKETS=0 fwd", bwd=False)
+    _check_vs_oracle(pb, got["bwd"], "REC_DIN_TICKETS=0 bwd", fwd=False)
+
+
+SPLIT_SHAPES = [(32, 152), (3, 100), (7, 33), (40, 64)]
+
+
+def _split_problem(B, T):
     g = torch.Generator(device=DEV).manual_seed(B * 1000 + T)
     Ei = Ec = 64
     n_item, n_cat = 500, 60
@@ -418,16 +562,41 @@ def test_tile_split_forward_and_backward_equal_the_per_sample_walk(engine_lib, m
     ab = [torch.randn(80, device=DEV, generator=g) * 0.1, torch.randn(40, device=DEV, generator=g) * 0.1,
           torch.randn(1, device=DEV, generator=g) * 0.1]
     dout = torch.randn(B, E, device=DEV, generator=g)
-    res = {}
-    for mode in ("1", "0"):
-        monkeypatch.setenv("REC_DIN_TILE_SPLIT", mode)
-        ws, saved = ops.Workspace(DEV), {}
-        out, attw, st = ops.din_attention_pool(hi, hc, ti, tc, mask, tabs[0], tabs[1], tabs[2], tabs[3], aw, ab,
-                                               saved=saved, ws=ws)
-        dh, dq = ops.din_attention_pool_bwd(hi, hc, ti, tc, tabs[0], tabs[1], tabs[2], tabs[3], aw, ab, attw, dout,
-                                            saved=saved)
-        res[mode] = [x.cpu().numpy() for x in (out, attw, dh, dq)]
-        assert int(st.item()) == 0
-    for a, b, name in zip(res["1"], res["0"], ("out", "att_weight", "d_hist", "d_tgt")):
+    p = dict(hi=hi, hc=hc, tis=ti, tcs=tc, mask=mask, dout=dout)
+    p.update({"tab%d" % k: t for k, t in enumerate(tabs)})
+    p.update({"aw%d" % k: t for k, t in enumerate(aw)})
+    p.update({"ab%d" % k: t for k, t in enumerate(ab)})
+    return {k: v.cpu().numpy() for k, v in p.items()}
+
+
+@pytest.fixture(scope="module")
+def split_off_child(engine_lib, tmp_path_factory):
+    """The per-sample walk of every SPLIT_SHAPES problem: REC_DIN_TILE_SPLIT=0 is latched by the first call of a
+    process, so it comes from ONE fresh child that runs all four."""
+    problems = {"b%dt%d" % s: (_split_problem(*s), (1, 1, 0)) for s in SPLIT_SHAPES}
+    return problems, _child(tmp_path_factory.mktemp("din_split_off"), dict(REC_DIN_TILE_SPLIT="0"), problems)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("B,T", SPLIT_SHAPES)
+def test_tile_split_forward_and_backward_equal_the_per_sample_walk(engine_lib, split_off_child, B, T):
+    """Few samples (din/config.yaml batch size 32: fewer than the chip has block slots): the forward runs one block per
+    32-position history tile and a combine launch rescales the per-tile softmax pieces (rec_din_attention_pool_fwd_ws),
+    the backward deals (sample, tile) pairs to the blocks.  Against the same kernels walking a sample's tiles in one
+    block (REC_DIN_TILE_SPLIT=0, in a child process: the switch is latched): pooled output, attention weights and both
+    gradients at fp32 rounding — and the two route logs differ, so the two halves are not one kernel compared with
+    itself.  Both halves are held to the float64 oracle as well."""
+    import _din_route_worker as W
+    problems, walked = split_off_child
+    p, _ = problems["b%dt%d" % (B, T)]
+    on, off = W.run(p, True, True, False), walked["b%dt%d" % (B, T)]
+    assert int(on["status"][0]) == 0 and int(off["status"][0]) == 0
+    assert on["fwd_route"].tolist() == [FWD_CT_SPLIT] and off["fwd_route"].tolist() == [FWD_CT_WALK]
+    assert on["bwd_route"].tolist() == ["din_bwd:ct:walk"] and off["bwd_route"].tolist() == ["din_bwd:ct:walk:nosplit"]
+    assert on["fwd_route"].tolist() != off["fwd_route"].tolist() and on["bwd_route"].tolist() != off["bwd_route"].tolist()
+    for name in ("out", "attw", "dh", "dq"):
+        a, b = on[name], off[name]
         np.testing.assert_allclose(a, b, rtol=0, atol=2e-6 * max(float(np.abs(b).max()), 1e-6), err_msg=name)
-    np.testing.assert_allclose(res["1"][1].sum(1), 1.0, atol=1e-5)
+    np.testing.assert_allclose(on["attw"].sum(1), 1.0, atol=1e-5)
+    _check_vs_oracle(p, off, "walk B %d T %d" % (B, T))
+    _check_vs_oracle(p, on, "split B %d T %d" % (B, T))
